@@ -10,11 +10,14 @@ N > 1: one process per GPU.  Started by `torch.distributed.run` (RANK / LOCAL_RA
 script is a rank; started bare with --gpus N > 1 it re-launches ITSELF under `torch.distributed.run --nproc-per-node N`
 (127.0.0.1 rendezvous, backend nccl = RCCL), so both ways of calling it give N ranks and `n_gpus: N`.
 
-A "step" is one pass of raw_encrypt over the batch (`value` = encrypts/s, whole job); the same K steps of raw_decrypt
-are timed as a second region ("decrypt").  Operands are resident in HBM before every timed region.  Ranks only meet
-at the barriers (the batch is embarrassingly sharded: no data-path collective in configs[1]).
+A "step" is one pass of raw_encrypt over the batch (`value` = encrypts/s, whole job; `ms_per_step` = one timed step).
+Operands are resident in HBM before every timed region.  Ranks only meet at the barriers (the batch is embarrassingly
+sharded: no data-path collective in configs[1]).  A plain run does only that: set-up, W warm-up steps, the K timed steps,
+the ciphertexts of the last step written out if --dump-outputs DIR is given, and the line.
 
-The same JSON line also carries
+--full adds everything else, with the exit code set by every comparison: the same K steps of raw_decrypt timed as a second
+region ("decrypt"), the full round trip and a strided sample of the batch checked against the libgmp oracle ("bit_exact"),
+and in the same JSON line
   ops          — configs[2]: _raw_add, _raw_mul by float-like 56-bit / int64 scalars and with 10 % negative scalars
                  (the inverse branch of phe/paillier.py:745-749), obfuscate — each over the whole batch, with its own
                  roofline entry and a strided sample checked against the libgmp oracle;
@@ -50,6 +53,17 @@ for p in (ROOT, PKG):
         sys.path.insert(0, p)
 
 METRIC = "Paillier 2048-bit encrypts/sec + decrypts/sec per node (bit-exact)"
+DUMP_ROWS = 16384          # --dump-outputs: 16 MB of float64 at 2048 bits, 24 MB at 3072
+
+
+def dump_outputs(path, be, c, rows):
+    """--dump-outputs: the ciphertexts the last timed encrypt step wrote, as DIR/ciphertexts.npy — float64 (exact for 32-bit
+    words), one row per ciphertext, its 32-bit words least significant first; the rows are a sample fixed by a seed (all of
+    them when the batch holds at most DUMP_ROWS), so that two builds of the project can be compared output for output."""
+    import numpy as np
+    idx = np.sort(np.random.default_rng(20261016).choice(rows, size=min(rows, DUMP_ROWS), replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ciphertexts.npy"), be.np(be.take(c, idx.tolist())).astype(np.float64))
 
 
 # ---- bookkeeping (checked on CPU by tests/test_bench_contract.py) -------------------------------------------------
@@ -229,6 +243,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also the decrypt region, the checks against libgmp and the other legs (ops, latency, config4, "
+                         "cpu_baseline, roofline); a plain run times the headline encrypt steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the ciphertexts of the last encrypt step (rank 0's shard; a fixed seeded "
+                         "sample of %d rows when the batch is larger) to DIR/ciphertexts.npy as float64" % DUMP_ROWS)
     ap.add_argument("--batch", type=int, default=1 << 20, help="plaintexts per GPU per step")
     ap.add_argument("--key-bits", type=int, default=2048, choices=[256, 1024, 2048, 3072])
     ap.add_argument("--cpu-sample", type=int, default=0, help="elements for the CPU baseline (0 = auto)")
@@ -262,7 +282,10 @@ def parse_args(argv=None):
     ap.add_argument("--inject-fault", choices=["cpu_baseline", "raw_add", "config4", "lib_allgather"], default=None,
                     help="TEST HOOK (tests/test_bench_contract.py): flip one bit of one result row of that leg after it was computed "
                          "and before it is checked — the run must then exit non-zero")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def relaunch_under_torchrun(args):
@@ -608,6 +631,37 @@ def main():
     for _ in range(args.warmup):
         enc_step()
     enc_dt, enc_launch_ms = timed(enc_step, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, be, c, B)
+    value = job_rows * args.steps / enc_dt
+    headline = None
+    if rank == 0:
+        info = ctx.info()
+        headline = {
+            "metric": METRIC, "value": value, "unit": "encrypts/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": enc_dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "u32 (29-bit limbs, v_mad_u64_u32 with 64-bit accumulate)",
+            "data": "synthetic" if be.name == "hip" else "synthetic, SELFTEST on the CPU wave emulator — not a measurement",
+            "rccl_ranks": dist.get_world_size() if use_dist else 1, "backend": be.dist_backend if use_dist else "single process",
+            "config": {"workload": "configs[1]: %d-bit key, %s, raw_encrypt%s, operands resident in HBM"
+                                   % (args.key_bits, ("%d-plaintext job cut into contiguous shards (strong scaling: %d on rank 0)" % (job_rows, B))
+                                      if strong else "%d-plaintext batch per GPU" % B, " then raw_decrypt" if args.full else ""),
+                       "key_bits": args.key_bits, "batch_per_gpu": B, "batch_whole_job": job_rows, "parallelism": "batch-sharded x%d" % world,
+                       "geometry": info},
+            "full": args.full,
+        }
+
+    def print_line(line):
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+
+    if not args.full:
+        print_line(headline)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     for _ in range(args.warmup):
         dec_step()
     dec_dt, dec_launch_ms = timed(dec_step, args.steps)
@@ -945,7 +999,6 @@ def main():
     if rank == 0:
         enc_mac, dec_mac = mac32_counts(args.key_bits)
         peak, sustained, peak_src = valu_peak_mac32()
-        info = ctx.info()
         split = info.get("engine_pub") == "split"
         kname = lambda limbs, eng, mode: "k_modexp_%s<%d,%d,%s>" % (("split" if eng == "split" else "uniform",) + divmod(limbs, 100) + (mode,))
         if "lane_limbs_pub" in info:
@@ -970,7 +1023,6 @@ def main():
         valu_unit, valu_src = pmc_valu_per_unit(enc_kernel) if args.key_bits == 2048 else (None, None)
         enc_kernel_s = sum(enc_launch_ms) / len(enc_launch_ms) * 1e-3
         dec_kernel_s = sum(dec_launch_ms) / len(dec_launch_ms) * 1e-3
-        value = job_rows * args.steps / enc_dt
         rate = lambda per_unit, seconds: per_unit * B / seconds if per_unit else None
         frac = lambda per_unit, seconds: per_unit * B / seconds / peak if per_unit else None
         roofline = {
@@ -1060,17 +1112,7 @@ def main():
                 ops["raw_add"]["roofline"]["form"] = counted["raw_add_form"]
             ops["raw_add"]["roofline"].update(hbm_algorithmic_GBps=add_bytes * ops["raw_add"]["value"] / world / 1e9,
                                               hbm_frac=add_bytes * ops["raw_add"]["value"] / world / 8e12)
-        out = {
-            "metric": METRIC, "value": value, "unit": "encrypts/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": enc_dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "u32 (29-bit limbs, v_mad_u64_u32 with 64-bit accumulate)",
-            "data": "synthetic" if be.name == "hip" else "synthetic, SELFTEST on the CPU wave emulator — not a measurement",
-            "rccl_ranks": dist.get_world_size() if use_dist else 1, "backend": be.dist_backend if use_dist else "single process",
-            "config": {"workload": "configs[1]: %d-bit key, %s, raw_encrypt then raw_decrypt, operands resident in HBM"
-                                   % (args.key_bits, ("%d-plaintext job cut into contiguous shards (strong scaling: %d on rank 0)" % (job_rows, B))
-                                      if strong else "%d-plaintext batch per GPU" % B),
-                       "key_bits": args.key_bits, "batch_per_gpu": B, "batch_whole_job": job_rows, "parallelism": "batch-sharded x%d" % world,
-                       "geometry": info},
+        out = {**headline,
             "decrypt": {"value": job_rows * args.steps / dec_dt, "unit": "decrypts/s",
                         "ms_per_step": dec_dt / args.steps * 1e3},
             "bit_exact": {"roundtrip_full_batch": roundtrip_ok, "strided_sample_vs_gmp_oracle": sample_ok,
@@ -1087,15 +1129,11 @@ def main():
     if use_dist:
         ok = max_over_ranks([0.0 if ok else 1.0])[0] == 0.0
 
-    def print_line():
-        if rank == 0:
-            sys.stdout.flush()
-            os.write(json_fd, (json.dumps(out) + "\n").encode())
-
     if lib_state is not None:
-        ok = library_allgather_leg(args, be, native, dist, use_dist, rank, world, lib_state, out, ok, print_line, barrier, max_over_ranks)
+        ok = library_allgather_leg(args, be, native, dist, use_dist, rank, world, lib_state, out, ok, lambda: print_line(out),
+                                   barrier, max_over_ranks)
         lib_state = None
-    print_line()
+    print_line(out)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

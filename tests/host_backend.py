@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: a libgmp-backed stand-in for phe._native.Context, for tests of the HOST side that make thousands of
-scalar calls (the reference's own example file, tests/test_reference_example_verbatim.py).
+scalar calls (the call shape of the reference's federated example, tests/test_federated_example.py).
 
 tests/emu_backend.EmuContext runs the device headers on a 64-fiber wave emulator: faithful, and ~0.1-0.8 s per one-row call.
 This context answers the same calls from the checker (oracle/paillier_oracle: libgmp / CPython integers), so that what is under

@@ -3,7 +3,7 @@ executed multiply-add model follows the window sizes key_setup.h picks, and the 
 import os
 import sys
 
-from conftest import ROOT
+from conftest import ROOT, load_golden
 
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -89,8 +89,35 @@ def _run_bench(cmd, timeout=600):
     return json.loads(lines[0])
 
 
-SELFTEST = ["--selftest-emu", "--key-bits", "256", "--batch", "6", "--steps", "2", "--warmup", "1",
+# --full: these tests read the legs and checks a plain run leaves out
+SELFTEST = ["--selftest-emu", "--full", "--key-bits", "256", "--batch", "6", "--steps", "2", "--warmup", "1",
             "--config4-key-bits", "256", "--config4-total", "9"]
+
+
+def test_plain_line_times_the_headline_steps_only_and_dumps_its_outputs(tmp_path, c_oracle):
+    """A plain run (no --full) sets up, warms up, times --steps encrypt steps and prints the headline line: no decrypt region,
+    no libgmp checks, no other legs.  --dump-outputs DIR holds the ciphertexts of the last timed step as float64, the same
+    from run to run, and they are the ciphertexts of the seeded inputs."""
+    import numpy as np
+    from phe import _native as native
+    plain = ["--selftest-emu", "--key-bits", "256", "--batch", "6", "--steps", "3", "--warmup", "1"]
+    dumps = []
+    for run in ("a", "b"):
+        out = _run_bench([sys.executable, "bench.py"] + plain + ["--dump-outputs", str(tmp_path / run)])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["full"] is False and out["n_gpus"] == 1
+        assert out["unit"] == "encrypts/s" and out["higher_is_better"] is True and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 6 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert out["metric"] == bench.METRIC and out["dtype"].startswith("u32")
+        assert not {"decrypt", "bit_exact", "roofline", "ops", "latency", "config4", "cpu_baseline"} & set(out)
+        assert os.listdir(str(tmp_path / run)) == ["ciphertexts.npy"]
+        dumps.append(np.load(str(tmp_path / run / "ciphertexts.npy")))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (6, 16) and np.array_equal(dumps[0], dumps[1])
+    be = bench.EmuSelftestBackend(0)
+    key = load_golden(256)
+    n = int(key["n"], 16)
+    m, r = be.rand(6, 8, 1234), be.rand(6, 8, 1235)
+    bench.clamp_operands(m, r, 8, n)
+    assert np.array_equal(dumps[0], c_oracle.encrypt(native.int_to_limbs(n, 8), m, r).astype(np.float64))
 
 
 def _check_two_rank_line(out):
@@ -201,8 +228,8 @@ def test_a_library_allgather_that_hangs_does_not_cost_the_line():
 
 
 def test_sample_sizes_of_the_default_line():
-    """what a default run checks against libgmp: 4,096 strided rows of the headline batch, of every ops result and of the
-    configs[3] job (plus its shard boundaries)"""
+    """what a --full run checks against libgmp by default: 4,096 strided rows of the headline batch, of every ops result and of
+    the configs[3] job (plus its shard boundaries)"""
     a = bench.parse_args([])
     assert (a.oracle_sample, a.ops_sample, a.config4_sample) == (4096, 4096, 4096) and a.inject_fault is None
 

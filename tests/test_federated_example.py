@@ -51,14 +51,28 @@ def test_scalar_api_protocol_on_gpu(key_bits, capsys):
     """BASELINE configs[4] in the call shape of the file it names (2,750 scalar `encrypt`, 2,200 scalar `+`, 550 scalar `decrypt`,
     examples/federated_learning_with_encryption.py:122-133, :213-225) on the real device, at the file's own 1024 bits (:257) and
     at the 2048 bits configs[4] asks for.  The reference file itself cannot be shipped to the GPU box (the reference may not
-    travel in any form: DESIGN §1 "configs[4]"); tests/test_reference_example_verbatim.py runs THAT file verbatim against this
-    same drop-in in the build container, so the two together pin file -> drop-in API (there) and drop-in API -> MI355X (here)."""
+    travel in any form: DESIGN §1 "configs[4]"); test_scalar_api_protocol_full_run_on_libgmp_stand_in runs the same call shape
+    on the CPU, so the two together pin the drop-in's Python layer (there) and drop-in API -> MI355X (here)."""
     errors, elapsed, calls = fed.run_scalar(key_length=key_bits, verbose=True)
     out = capsys.readouterr().out
     assert calls == {"encrypt": 2750, "add": 2200, "decrypt": 550}
     assert ["%.2f" % e for e in errors] == ["3775.50"] * 5, out
     assert np.allclose(errors, plaintext_rounds(fed.N_ROUNDS), rtol=1e-9)
     sys.stderr.write("configs[4], scalar API, %d-bit key on the GPU: %.2f s\n%s" % (key_bits, elapsed, out))
+
+
+def test_scalar_api_protocol_full_run_on_libgmp_stand_in(monkeypatch):
+    """BASELINE configs[4] in the call shape of the file it names (python-paillier's examples/federated_learning_with_encryption.py:
+    scalar `encrypt`, `+` and `decrypt`, its own 1024-bit key, 50 rounds) on the CPU, the hot calls answered by the libgmp stand-in
+    (tests/host_backend.py): what is under test is the drop-in's Python layer — object API, encoding, exponent alignment,
+    obfuscation, engine plumbing.  It must print what that file prints: the five local-only errors and 3775.50 for every hospital."""
+    import host_backend
+    host_backend.install(monkeypatch)
+    assert ["%.2f" % e for e in fed.local_only()] == ["3810.44", "3982.58", "3569.32", "4144.15", "3848.39"]
+    errors, _, calls = fed.run_scalar(key_length=1024, verbose=False)
+    assert calls == {"encrypt": 2750, "add": 2200, "decrypt": 550}
+    assert ["%.2f" % e for e in errors] == ["3775.50"] * 5
+    assert np.allclose(errors, plaintext_rounds(fed.N_ROUNDS), rtol=1e-9)
 
 
 def test_scalar_api_protocol_one_round_on_emulator(monkeypatch):

@@ -12,8 +12,10 @@ from conftest import ROOT
 
 
 @pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="needs hipcc (cross-compile only)")
-def test_static_tally_of_the_sweep_loops_agrees_with_the_closed_form():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "static_mad_tally.py")], capture_output=True, text=True, timeout=900)
+def test_static_tally_of_the_sweep_loops_agrees_with_the_closed_form(tmp_path):
+    # the assembly goes to a file of fixed name in the temporary directory: this test's own, not one another user may hold
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "static_mad_tally.py")], capture_output=True, text=True, timeout=900,
+                         env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert res.returncode == 0, res.stdout + res.stderr
     out = res.stdout
     # round 5: a square's first word takes the symmetric half of X0*X0 — 10 of 18 limbs per lane and row: 1152 multiply-adds per trip

@@ -12,4 +12,4 @@ for bits in 1024 3072 4096; do
 done
 unset PHE_HIP_WAVE_TAIL_PER_CU
 cat $out/sweep_keys.txt
-timeout 600 python bench.py > $out/bench_1M.json 2> $out/bench_1M.err; tail -c 600 $out/bench_1M.json
+timeout 600 python bench.py --full > $out/bench_1M.json 2> $out/bench_1M.err; tail -c 600 $out/bench_1M.json

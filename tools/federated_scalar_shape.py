@@ -2,7 +2,7 @@
 """The call shape of BASELINE.json configs[4]'s file on the GPU, through the drop-in's SCALAR API.
 
 /root/reference/examples/federated_learning_with_encryption.py is not on the GPU box, so the file itself cannot run there
-(tests/test_reference_example_verbatim.py runs it verbatim in the build container).  What it does to the backend is, per run
+(tests/test_federated_example.py runs its call shape on the CPU).  What it does to the backend is, per run
 (5 hospitals, 50 rounds, 10 features + intercept = 11 gradient components; :122-133, :213-225):
 
     2,750 x public_key.encrypt(float)          one at a time      (:123  [public_key.encrypt(i) for i in gradient])

@@ -10,7 +10,7 @@ for G in 0 4 8 16; do
 done
 cat $O/batch_sweep_g0.txt
 timeout 300 python tools/bench_sweep.py --group 2 --ops decrypt --table > $O/batch_sweep_g2_decrypt.json 2> $O/batch_sweep_g2_decrypt.txt; echo "sweep g2 rc=$?"
-timeout 900 python bench.py --steps 3 --warmup 1 > $O/bench_1M.json 2> $O/bench_1M.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 3 --warmup 1 > $O/bench_1M.json 2> $O/bench_1M.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.load(open("$O/bench_1M.json")); r=d["roofline"]

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 O=gpurun_out/${TAG:-r05c}; mkdir -p $O; R=$PWD
 L=$R/python-paillier_amd/lib
 run() { # name lib
-  PHE_HIP_LIB=$2 timeout 300 python bench.py --steps 3 --warmup 1 --no-ops --no-cpu-baseline --no-config4 --oracle-sample 64 2>/dev/null | python -c "
+  PHE_HIP_LIB=$2 timeout 300 python bench.py --full --steps 3 --warmup 1 --no-ops --no-cpu-baseline --no-config4 --oracle-sample 64 2>/dev/null | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

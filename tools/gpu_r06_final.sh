@@ -7,12 +7,12 @@ O=gpurun_out/${TAG:-r06f}; mkdir -p $O
 export TMPDIR=/tmp
 timeout 200 python __graft_entry__.py smoke; echo "smoke rc=$?"
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; grep -E "passed|failed" $O/pytest_gpu.txt | tail -2
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_1M.json 2> $O/bench_1M.err; echo "bench rc=$?"
-timeout 400 python bench.py --key-bits 1024 --steps 5 --warmup 2 --no-config4 > $O/bench_1024.json 2>/dev/null; echo "1024 rc=$?"
-timeout 400 python bench.py --key-bits 3072 --batch 262144 --steps 2 --warmup 1 --no-config4 > $O/bench_3072.json 2>/dev/null; echo "3072 rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_1M.json 2> $O/bench_1M.err; echo "bench rc=$?"
+timeout 400 python bench.py --full --key-bits 1024 --steps 5 --warmup 2 --no-config4 > $O/bench_1024.json 2>/dev/null; echo "1024 rc=$?"
+timeout 400 python bench.py --full --key-bits 3072 --batch 262144 --steps 2 --warmup 1 --no-config4 > $O/bench_3072.json 2>/dev/null; echo "3072 rc=$?"
 # every row of the headline batch against libgmp (not a bench line: one step, the oracle takes ~6 minutes on 16 cores)
-timeout 900 python bench.py --steps 1 --warmup 0 --oracle-sample 1048576 --no-ops --no-config4 --no-cpu-baseline > $O/every_row_vs_libgmp_2048_1M.json 2>/dev/null; echo "every-row rc=$?"
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $R/$O/prof_kt -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $R/$O/bench_1M_under_tracer.json 2> $R/$O/prof_kt.log; echo "kt rc=$?")
+timeout 900 python bench.py --full --steps 1 --warmup 0 --oracle-sample 1048576 --no-ops --no-config4 --no-cpu-baseline > $O/every_row_vs_libgmp_2048_1M.json 2>/dev/null; echo "every-row rc=$?"
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $R/$O/prof_kt -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $R/$O/bench_1M_under_tracer.json 2> $R/$O/prof_kt.log; echo "kt rc=$?")
 python tools/rocprof_summarize.py $O/prof_kt > $O/rocprofv3_kernel_trace_stats_1M.txt 2>&1; rm -rf $O/prof_kt
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/prof_kt_dec -- python $R/bench.py --batch 262144 --steps 3 --warmup 1 --no-cpu-baseline --no-ops --no-config4 --only decrypt > $R/$O/prof_kt_dec.log 2>&1; echo "kt dec rc=$?")
 python tools/rocprof_summarize.py $O/prof_kt_dec > $O/rocprofv3_kernel_trace_stats_decrypt_only.txt 2>&1; rm -rf $O/prof_kt_dec

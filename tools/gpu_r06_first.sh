@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout 200 python __graft_entry__.py smoke; echo "smoke rc=$?"
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest_gpu.txt
 timeout 400 python -m pytest tests/test_federated_example.py -m gpu -q -s -k scalar > $O/federated_scalar_api_gpu.txt 2>&1; echo "federated rc=$?"; grep -E "configs\[4\]|Hospital|rounds" $O/federated_scalar_api_gpu.txt | head -20
-timeout 600 python bench.py > $O/bench_1M.json 2> $O/bench_1M.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $O/bench_1M.json 2> $O/bench_1M.err; echo "bench rc=$?"
 timeout 300 python tools/bench_api.py 1048576 > $O/bench_api_1M.json 2> $O/bench_api.err; echo "api rc=$?"; cat $O/bench_api_1M.json | head -c 1500
 for grp in 0 4 8; do
   timeout 400 python tools/bench_sweep.py --key-bits 3072 --group $grp --min 20 --max 20 --ops encrypt,decrypt,mul --budget-ms 4000 --table > $O/pin3072_g$grp.json 2> $O/pin3072_g$grp.txt
