@@ -345,10 +345,16 @@ PHE_DEV void tile_settle_blocks(const TableMulArgs& A, uint32_t* tile, uint32_t*
             yd += (double)c * w;
         }
         const double qe = yd * A.inv, qd = __builtin_floor(qe), frac = qe - qd;
-        // The estimate is within 2^-13 of y / N (y / N < 2^38; the limbs below `base` weigh < 2^-70 of a unit; W^base / N, the sum of the
-        // four limbs and the product are rounded to 53 bits: 3 x 2^-15).  Where its fraction keeps 2^-11 away from 0 and 1 the floor IS
-        // floor(y / N): ONE candidate, r = y - floor N, already below N.  Every wave sees the same limbs of all 64 elements, so the
-        // workgroup agrees without asking; a tile with an element too close to call (1 in 2^10) takes the three candidates.
+        // The estimate is within 2^-12 of y / N, y / N < 2^38.  What it does not read — the limbs below `base` (< W^base) and a block
+        // carry < 2^38 that enters at most one limb below `base` (< 2^9 W^base) — weighs up to (2^9 + 1) W^base / N of a quotient unit:
+        // about 2^-20, since W^base / N <= 2^-29 (not the 2^-70 an earlier version of this comment claimed).  What it reads is rounded to
+        // 53 bits up to six times — W^base / N twice (the top 64 bits of N to a double, the reciprocal), the sums of the limbs and of the
+        // carry three times, the product once; fewer where the compiler contracts a multiply-add — each time by 2^-53 of a value
+        // below 2^38: 6 x 2^-15 < 2^-12.4.  Where its fraction keeps 2^-11 away from 0 and 1 the floor IS floor(y / N): ONE
+        // candidate, r = y - floor N, already below N.  Every wave sees the same limbs of all 64 elements, so the workgroup agrees
+        // without asking; a tile with an element too close to call (1 in 2^10) takes the three candidates.  (tests/test_emu_settle.py
+        // drives this function alone at these limits: quotients 0, 1 and 2^38 - 1, block carries of 2^38 - 1 in every block, fractions
+        // a few steps either side of 2^-11 and of 1 - 2^-11.)
         fast = wave::ballot(!(qd >= 1.0 && frac > 0.00048828125 && frac < 0.99951171875)) == 0;
         const uint64_t q = fast ? (uint64_t)qd : (qd >= 1.0 ? (uint64_t)qd - 1u : 0u);  // (the estimate may be one too high: never let r go negative)
         q0 = (uint32_t)q & kLimbMask;

@@ -445,8 +445,75 @@ static void run_mul_tile(TableMulArgs A, const host::TableMulPack& T, int n_bloc
         });
     }
 }
+// tile_settle_blocks (mul_tile.h) on its own: ONE tile whose fold results are GIVEN — element i's digits y[i][0 .. S) (what the
+// fold left in the blocks: < 2^29 each) and what left each block, ycarry[i][w] (< 2^38) — so that a test can hand the settle
+// digits, block carries and quotients that no product of two rows reaches.  B <= 64 live elements; the lanes past them repeat the
+// last one, as the kernel's clamped `item` does.
+template <int L, int W>
+static void run_settle_blocks(TableMulArgs A, const host::TableMulPack& T, const uint32_t* ydig, const uint64_t* ycar_in) {
+    using TS = TileShape<L, W>;
+    if (T.tile_waves != W || T.S != TS::S) throw std::runtime_error("the pack is cut for another workgroup shape");
+    std::vector<Words4> lds((size_t)tile_lds_words<L, W>() / 4 + 1);
+    uint32_t* tile = (uint32_t*)lds.data();
+    for (size_t i = 0; i < lds.size() * 4; ++i) tile[i] = 0xdeadbeefu;   // LDS is not zero on the device either
+    uint32_t* prod_carry = tile + TS::kRows * kTile;
+    uint32_t* top = prod_carry + 2 * 2 * W * kTile;
+    uint32_t* fold_carry = top + kTile * kTableRowSlack;
+    uint32_t* cst = fold_carry + 2 * W * kTile;
+    memcpy(cst, T.n.data(), TS::S * 4);
+    memcpy(cst + TS::S, T.ncomp.data(), TS::S * 4);
+    memcpy(cst + 2 * TS::S, T.ncomp1.data(), TS::S * 4);
+    wave::run_block(W, [&](uint32_t wv, uint32_t lane) {
+        const bool live = lane < A.batch;
+        const uint64_t item = live ? lane : A.batch - 1;
+        uint32_t y[TS::CW];
+        for (int k = 0; k < TS::CW; ++k) y[k] = ydig[item * TS::S + wv * TS::CW + (uint32_t)k];
+        tile_settle_blocks<L, W>(A, tile, prod_carry, top, fold_carry, cst, wv, lane, y, ycar_in[item * W + wv], item, live, []() {});
+    });
+}
 static int g_tile_mul = 0, g_tile_blocks = 2;
 extern "C" {
+
+// non-zero flag words posted by the settle's carry look-ahead since the last reset (wave_emu.h flag_counter: emulator only)
+uint64_t emu_flag_count(int reset) {
+    const uint64_t v = wave::flag_counter();
+    if (reset) wave::flag_counter() = 0;
+    return v;
+}
+
+// the tile product's constants for this modulus and workgroup shape: geom = {L, S, split P, base, digits D}, inv = W^base / N as the
+// kernel gets it.  rc 2: no tiles for this modulus on `waves` waves
+int emu_table_mul_info(const uint32_t* N, int limbs, int waves, int* geom, double* inv) {
+    try {
+        const host::TableMulPack T = host::build_table_mul(host::big_from(N, limbs, limbs), limbs, true, waves);
+        if (!T.ok() || !T.tiles()) return 2;
+        geom[0] = T.L; geom[1] = T.S; geom[2] = T.split; geom[3] = T.base; geom[4] = T.digits;
+        *inv = T.inv;
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// out[i] = (sum_k y[i][k] W^k + sum_w ycarry[i][w] W^(CW (w + 1))) mod N by tile_settle_blocks alone, B <= 64 elements of one tile
+int emu_settle_blocks(const uint32_t* N, int limbs, int waves, const uint32_t* y, const uint64_t* ycarry, uint32_t* out, uint64_t B) {
+    try {
+        if (B == 0 || B > 64 || limbs % 4) return 2;
+        const host::TableMulPack T = host::build_table_mul(host::big_from(N, limbs, limbs), limbs, true, waves);
+        if (!T.ok() || !T.tiles()) return 2;
+        std::vector<Words4> o4((size_t)B * limbs / 4 + 1);
+        TableMulArgs A;
+        memset(&A, 0, sizeof A);
+        A.n = T.n.data(); A.ncomp = T.ncomp.data(); A.ncomp1 = T.ncomp1.data(); A.table = T.table_cols.data();
+        A.inv = T.inv; A.split = T.split; A.digits = T.digits; A.base = T.base; A.digits_padded = T.digits_padded; A.tile_waves = T.tile_waves;
+        A.out = (uint32_t*)o4.data();
+        A.a_stride = A.b_stride = A.out_stride = (size_t)limbs; A.limbs = limbs; A.batch = B;
+        if (waves == 8 && T.L == 9) run_settle_blocks<9, 8>(A, T, y, ycarry);
+        else if (waves == 16 && T.L == 9) run_settle_blocks<9, 16>(A, T, y, ycarry);
+        else if (waves == 16 && T.L == 14) run_settle_blocks<14, 16>(A, T, y, ycarry);
+        else return 2;
+        memcpy(out, o4.data(), (size_t)B * limbs * 4);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
 
 // e: 0 = mul_table.h (table in LDS), 1 = mul_tile.h on 16 waves, 2 = mul_tile.h on 8 waves (S = 8 L: the shape of 1024-bit keys)
 void emu_set_tile_mul(int e, int blocks) { g_tile_mul = (e == 1 || e == 2) ? e : 0; g_tile_blocks = blocks > 0 ? blocks : 2; }

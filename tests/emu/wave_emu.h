@@ -217,6 +217,15 @@ inline uint64_t& mad_counter() {
     return count;
 }
 
+// TEST-ONLY look-ahead counter (the device has none): the settle of mul_tile.h posts a block's generate / propagate bits with
+// lds_or, and only where some element of the tile has one.  Every lds_or of a NON-ZERO word is counted, so that a test can state
+// that the carry look-ahead ran on a tile (and that it did not on ordinary rows) instead of assuming it.  Counted like the
+// multiply-adds: per host thread, run_block adds what its wave threads counted to the caller's.
+inline uint64_t& flag_counter() {
+    static thread_local uint64_t count = 0;
+    return count;
+}
+
 // run `body(wave, lane)` for the waves of one workgroup, one host thread per wave; block_barrier() joins them
 inline void run_block(int n_waves, const std::function<void(uint32_t, uint32_t)>& body) {
     pthread_barrier_t bar;
@@ -226,23 +235,26 @@ inline void run_block(int n_waves, const std::function<void(uint32_t, uint32_t)>
         const std::function<void(uint32_t, uint32_t)>* body;
         uint32_t wave;
         uint64_t mads;
+        uint64_t flags;
     };
     std::vector<pthread_t> th((size_t)n_waves);
     std::vector<Arg> args((size_t)n_waves);
     for (int w = 0; w < n_waves; ++w) {
-        args[(size_t)w] = Arg{&body, (uint32_t)w, 0};
+        args[(size_t)w] = Arg{&body, (uint32_t)w, 0, 0};
         pthread_create(&th[(size_t)w], nullptr, [](void* p) -> void* {
             Arg* a = (Arg*)p;
             const uint32_t wv = a->wave;
             const auto* fn = a->body;
             run_wave([&](uint32_t lane) { (*fn)(wv, lane); });
             a->mads = mad_counter();
+            a->flags = flag_counter();
             return nullptr;
         }, &args[(size_t)w]);
     }
     for (int w = 0; w < n_waves; ++w) {
         pthread_join(th[(size_t)w], nullptr);
         mad_counter() += args[(size_t)w].mads;
+        flag_counter() += args[(size_t)w].flags;
     }
     block_barrier_object() = nullptr;
     pthread_barrier_destroy(&bar);
@@ -298,7 +310,10 @@ template <class T>
 inline T* reread_vptr(T* p) { return p; }
 inline uint32_t reread(uint32_t x) { return x; }  // see wave_gfx950.h: an optimisation barrier on the device, nothing here
 inline uint64_t reread64(uint64_t x) { return x; }
-inline void lds_or(uint32_t* p, uint32_t v) { __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }  // (the waves of a workgroup are host threads)
+inline void lds_or(uint32_t* p, uint32_t v) {  // (the waves of a workgroup are host threads)
+    if (v != 0u) ++flag_counter();
+    __atomic_fetch_or(p, v, __ATOMIC_RELAXED);
+}
 typedef uint32_t lds_u32;  // wave_gfx950.h: an LDS-address-space pointer on the device
 inline lds_u32* as_lds(uint32_t* p) { return p; }
 inline lds_u32* reread_lds(uint32_t* p) { return p; }

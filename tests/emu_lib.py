@@ -114,6 +114,39 @@ class Emu:
         self._ck(rc)
         return out
 
+    def mad_count(self, reset=True):
+        """multiply-add lane-operations since the last reset (wave_emu.h mad_counter)"""
+        self.L.emu_mad_count.restype = ctypes.c_uint64
+        return int(self.L.emu_mad_count(1 if reset else 0))
+
+    def flag_count(self, reset=True):
+        """non-zero generate / propagate words the settle of mul_tile.h posted since the last reset (wave_emu.h flag_counter: the
+        emulator's own count — the device has none)"""
+        self.L.emu_flag_count.restype = ctypes.c_uint64
+        return int(self.L.emu_flag_count(1 if reset else 0))
+
+    def table_mul_info(self, N, waves):
+        """the tile product's constants for this modulus: {L, S, split, base, digits, inv}; None where it offers no tiles"""
+        geom = (ctypes.c_int * 5)()
+        inv = ctypes.c_double(0.0)
+        rc = self.L.emu_table_mul_info(P(N), N.shape[0], waves, geom, ctypes.byref(inv))
+        if rc == 2:
+            return None
+        self._ck(rc)
+        return dict(zip(("L", "S", "split", "base", "digits"), list(geom)), inv=inv.value)
+
+    def settle_blocks(self, N, y, ycarry, waves):
+        """csrc/mul_tile.h tile_settle_blocks on one tile of GIVEN fold results: y (rows, S) digits of 29 bits, ycarry (rows, W)
+        uint64 block carries -> (rows, limbs) words of (sum y W^k + sum ycarry W^(CW (w + 1))) mod N; at most 64 rows"""
+        y = np.ascontiguousarray(y, np.uint32)
+        ycarry = np.ascontiguousarray(ycarry, np.uint64)
+        out = np.zeros((y.shape[0], N.shape[0]), np.uint32)
+        rc = self.L.emu_settle_blocks(P(N), N.shape[0], waves, P(y), P(ycarry), P(out), ctypes.c_uint64(y.shape[0]))
+        if rc == 2:
+            return None
+        self._ck(rc)
+        return out
+
     def add_plain(self, n, c, m):
         out = np.zeros_like(c)
         self._ck(self.L.emu_add_plain(P(n), n.shape[0], P(c), P(m), P(out), ctypes.c_uint64(c.shape[0])))

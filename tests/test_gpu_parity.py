@@ -5,12 +5,14 @@
 and, at sizes the CPU cannot check exhaustively, through size-independent properties
 (decrypt∘encrypt = id, homomorphism, inverse*self = 1).
 Nothing here reads /root/reference."""
+import math
 import random
 import sys
 
 import numpy as np
 import pytest
 
+import adversarial as adv
 from conftest import PKG, load_golden, load_kat
 
 if PKG not in sys.path:
@@ -776,3 +778,209 @@ def test_scaled_modulus_path_gives_the_plain_path_bits(native, c_oracle, key_bit
     plain = make()
     assert np.array_equal(plain.encrypt(m, r), c)
     assert np.array_equal(plain.obfuscate(c, r), ob)
+
+
+# ---- adversarial residues for every kernel that computes a * b mod n^2 (tests/adversarial.py) -----------------------------------------
+# The result t is chosen first, a is a random unit, b = t / a: the kernel must return exactly t, and every row is compared.  The
+# residues have zero and all-ones column blocks (the settle's carry look-ahead: generate / propagate), sit next to 0 and n^2 (three
+# candidates instead of one) and around n^2 * 2^-11 (the guard of the quotient estimate, where the device's contraction of the
+# estimate's multiply-adds may put a row on the other side than the CPU emulator does: the residue must be right on either side).
+# tests/test_emu_settle.py asserts on the emulator that these rows run the look-ahead branches and which path each tile takes; on
+# the device neither can be observed without changing the kernel, so here only the kernel taken (the launch record) is asserted.
+
+ADV_MODULI = [("golden", 1024), ("high", 1024), ("golden", 2048), ("low", 2048), ("off-grid", 1920), ("golden", 3072), ("high", 3072)]
+
+
+def adv_modulus(kind, key_bits):
+    """-> n, words of n: the golden key, an extremal modulus of its width (tests/adversarial.py extremal_moduli), or a seeded odd
+    number off the limb grid (the product kernels need no primes; Context(n, n_limbs=...) is public-only)"""
+    rng = random.Random(7 * key_bits)
+    if kind == "golden":
+        n = H(load_golden(key_bits)["n"])
+    elif kind == "off-grid":
+        n = rng.getrandbits(key_bits) | (1 << (key_bits - 1)) | 1
+    else:
+        n = adv.extremal_moduli(key_bits, rng)[kind]
+    assert n.bit_length() == key_bits
+    return n, -(-key_bits // 128) * 4
+
+
+def device_cu_count(ctx):
+    """compute units of device 0, from the HIP runtime the library itself runs on (hipDeviceAttributeMultiprocessorCount = 63 in
+    hip_runtime_api.h; what phe_hip.hip reads as prop.multiProcessorCount), cross-checked with the context's own rows in flight"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    v = ctypes.c_int(0)
+    assert hip.hipDeviceGetAttribute(ctypes.byref(v), 63, 0) == 0 and 16 <= v.value <= 1024, v.value
+    assert ctx.info()["rows_in_flight"] % v.value == 0
+    return v.value
+
+
+def adv_check(native, got, want, fam, what):
+    bad = adv.first_mismatch(native.limbs_to_ints(got), want, fam)
+    assert bad is None, "%s: %s" % (what, bad)
+
+
+def adv_mulmod_dev(native, ctx, a, b):
+    """-> the product rows (device-pointer entry), checked to be the same in place (out = a)"""
+    from phe._device import DeviceArray
+    da, db = DeviceArray.from_host(ctx, a), DeviceArray.from_host(ctx, b)
+    out = DeviceArray(ctx, a.shape[0], a.shape[1])
+    ctx.mulmod_dev(da.ptr, db.ptr, out.ptr, a.shape[0])
+    ctx.sync()
+    path = ctx.last_launch()["path"]
+    got = out.to_host()
+    ctx.mulmod_dev(da.ptr, db.ptr, da.ptr, a.shape[0])
+    ctx.sync()
+    assert ctx.last_launch()["path"] == path
+    assert np.array_equal(da.to_host(), got), "in place differs"
+    return got, path
+
+
+@pytest.mark.parametrize("kind,key_bits", ADV_MODULI)
+def test_adversarial_residues_by_tiles(native, kind, key_bits):
+    """csrc/mul_tile.h on the device, all three tile shapes: 16384 rows (the switch to tiles) and 3 x (workgroups in flight) x 64 + 11
+    rows, so that every workgroup loops over at least three tiles (the double-buffered row window) and the last tile is ragged
+    with a Near row as its last live one.  Every family x tile layout of tests/adversarial.py, then whole tiles of the families in
+    turn.  The tile path asserted; every row against the residue it was built for, in place as well.  (That the look-ahead
+    branches run on these rows is asserted on the emulator, tests/test_emu_settle.py: the device offers no way to observe it
+    short of instrumenting the kernel.)"""
+    n, s1 = adv_modulus(kind, key_bits)
+    N, s2 = n * n, 2 * s1
+    CW, W = adv.tile_shape(N.bit_length())
+    ctx = native.Context(n, n_limbs=s1)
+    in_flight = device_cu_count(ctx) * (2 if W == 8 else 1)   # phe_hip.hip launch_mul: the grid's cap (kernels_t16.hip tile_blocks_per_cu)
+    rng = random.Random(key_bits + len(kind))
+    big = 3 * in_flight * 64 + 11
+    assert -(-big // 64) >= 3 * in_flight and big % 64 == 11
+    a, b, want, fam = adv.fill_batch(N, 32 * s2, CW, W, rng, big, n_root=n)
+    assert all(x * y % N == t for x, y, t in zip(a, b, want)) and fam[-1] == "Near"
+    al, bl = native.ints_to_limbs(a, s2), native.ints_to_limbs(b, s2)
+    for rows in (16384, big):
+        got, path = adv_mulmod_dev(native, ctx, al[:rows], bl[:rows])
+        assert path & ctx.PATH_TILE_MUL, (rows, path)
+        adv_check(native, got, want[:rows], fam[:rows], "%s %d, %d rows" % (kind, key_bits, rows))
+    assert len(got) == len(want) == big
+
+
+@pytest.mark.parametrize("kind,key_bits", [("golden", 1024), ("golden", 2048), ("low", 2048)])
+def test_adversarial_residues_by_the_table_in_lds(native, kind, key_bits, monkeypatch):
+    """csrc/mul_table.h (k_mulmod_table: floor(estimate) - 1, then conditional subtractions) on 8,192 and 16,383 rows of every family
+    and tile layout; 1024 bits as the neighbouring test reaches it (PHE_HIP_NO_TILE8 + PHE_HIP_TABLE_MUL_ANY_WIDTH).  The path
+    asserted, every row compared, in place as well."""
+    monkeypatch.setenv("PHE_HIP_TABLE_MUL_ANY_WIDTH", "1")
+    monkeypatch.setenv("PHE_HIP_NO_TILE8", "1")
+    n, s1 = adv_modulus(kind, key_bits)
+    N, s2 = n * n, 2 * s1
+    CW, W = adv.tile_shape(N.bit_length())
+    ctx = native.Context(n, n_limbs=s1)
+    rng = random.Random(key_bits + 2 * len(kind))
+    a, b, want, fam = adv.fill_batch(N, 32 * s2, CW, W, rng, 16383, n_root=n)
+    assert all(x * y % N == t for x, y, t in zip(a, b, want))
+    al, bl = native.ints_to_limbs(a, s2), native.ints_to_limbs(b, s2)
+    for rows in (8192, 16383):
+        got, path = adv_mulmod_dev(native, ctx, al[:rows], bl[:rows])
+        assert path & ctx.PATH_TABLE_MUL and not path & ctx.PATH_TILE_MUL, (rows, path)
+        adv_check(native, got, want[:rows], fam[:rows], "%s %d, %d rows" % (kind, key_bits, rows))
+
+
+@pytest.mark.parametrize("kind,key_bits", [("golden", 1024), ("golden", 2048), ("high", 2048), ("golden", 3072)])
+def test_adversarial_residues_by_the_staged_montgomery_kernels(native, kind, key_bits, monkeypatch):
+    """The two-Montgomery-product kernels (PHE_HIP_NO_TABLE_MUL) on 8,191 rows and on a small batch: 0, 1 and n^2 - 1 (the Near
+    family) are where a conditional subtraction goes wrong, the Wide rows are operands above n^2.  Every row compared."""
+    monkeypatch.setenv("PHE_HIP_NO_TABLE_MUL", "1")
+    n, s1 = adv_modulus(kind, key_bits)
+    N, s2 = n * n, 2 * s1
+    CW, W = adv.tile_shape(N.bit_length())
+    ctx = native.Context(n, n_limbs=s1)
+    rng = random.Random(key_bits + 3 * len(kind))
+    a, b, want, fam = adv.fill_batch(N, 32 * s2, CW, W, rng, 8191, n_root=n)
+    assert all(x * y % N == t for x, y, t in zip(a, b, want))
+    al, bl = native.ints_to_limbs(a, s2), native.ints_to_limbs(b, s2)
+    for rows in (8191, 75):
+        lo = 0 if rows == 8191 else 8 * 64                    # (the small batch: the tile of Near rows and eleven more)
+        got, path = adv_mulmod_dev(native, ctx, al[lo:lo + rows], bl[lo:lo + rows])
+        assert not path & (ctx.PATH_TABLE_MUL | ctx.PATH_TILE_MUL), (rows, path)
+        adv_check(native, got, want[lo:lo + rows], fam[lo:lo + rows], "%s %d, %d rows" % (kind, key_bits, rows))
+    assert set(fam[8 * 64:9 * 64]) == {"Near"}
+
+
+@pytest.mark.parametrize("key_bits", [1024, 2048, 3072])
+def test_adversarial_residues_give_equal_bits_on_every_product_kernel(native, key_bits, monkeypatch):
+    """One batch a width through the tile kernel, the table-in-LDS kernel (none at 3072 bits: its table does not fit) and the
+    staged Montgomery kernels: identical arrays, and the residues the rows were built for."""
+    g = load_golden(key_bits)
+    n, s1 = H(g["n"]), key_bits // 32
+    N, s2 = n * n, 2 * s1
+    CW, W = adv.tile_shape(N.bit_length())
+    monkeypatch.setenv("PHE_HIP_TABLE_MUL_ANY_WIDTH", "1")
+    tile = native.Context(n, n_limbs=s1)                      # (1024 bits: the 8-wave tiles)
+    monkeypatch.setenv("PHE_HIP_NO_TILE8", "1")
+    monkeypatch.setenv("PHE_HIP_NO_TILE_MUL", "1")
+    table = native.Context(n, n_limbs=s1)
+    monkeypatch.setenv("PHE_HIP_NO_TABLE_MUL", "1")
+    staged = native.Context(n, n_limbs=s1)
+    rng = random.Random(key_bits + 41)
+    rows = 16384 + 11
+    a, b, want, fam = adv.fill_batch(N, 32 * s2, CW, W, rng, rows, n_root=n)
+    assert all(x * y % N == t for x, y, t in zip(a, b, want))
+    al, bl = native.ints_to_limbs(a, s2), native.ints_to_limbs(b, s2)
+    by_tiles, path = adv_mulmod_dev(native, tile, al, bl)
+    assert path & tile.PATH_TILE_MUL
+    adv_check(native, by_tiles, want, fam, "tiles %d" % key_bits)
+    by_staged, path = adv_mulmod_dev(native, staged, al, bl)
+    assert not path & (tile.PATH_TABLE_MUL | tile.PATH_TILE_MUL)
+    assert np.array_equal(by_tiles, by_staged)
+    if key_bits < 3072:
+        by_table, path = adv_mulmod_dev(native, table, al, bl)
+        assert path & tile.PATH_TABLE_MUL and not path & tile.PATH_TILE_MUL
+        assert np.array_equal(by_tiles, by_table)
+
+
+@pytest.mark.parametrize("key_bits", [1024, 2048])
+def test_adversarial_residues_through_the_sums_of_resident_vectors(native, key_bits):
+    """The forms EncryptedVector.__add__ takes on resident vectors (phe/ciphertext.py __add__ / sum): the Montgomery-debt product
+    (montmul_dev, the debt settled when the rows are looked at), the pair-form product (pair_mul_dev) and sum()'s pairwise tree
+    (montmul_tree_dev), on vectors whose element-wise products are the family residues; the tree on leaves whose first level gives
+    family residues and whose second level gives 1 and n^2 - 1 at inner nodes.  The ciphertext integers against Python's."""
+    from phe import paillier
+    from phe.ciphertext import EncryptedVector
+    g = load_golden(key_bits)
+    pub = paillier.PaillierPublicKey(H(g["n"]))
+    n, N = pub.n, pub.nsquare
+    CW, W = adv.tile_shape(N.bit_length())
+    rng = random.Random(key_bits + 43)
+    a, b, want, fam = adv.adversarial_pairs(N, 2 * key_bits, CW, W, rng, "whole", families=[f for f in adv.FAMILIES if f != "Wide"], n_root=n)
+    a2, b2, want2, fam2 = adv.adversarial_pairs(N, 2 * key_bits, CW, W, rng, "ragged_near", n_root=n)
+    a, b, want, fam = a + a2, b + b2, want + want2, fam + fam2
+    assert all(x * y % N == t for x, y, t in zip(a, b, want)) and max(max(a), max(b)) < N     # (ciphertexts: residues)
+    va = EncryptedVector.from_ciphertexts(pub, a).to_device()
+    vb = EncryptedVector.from_ciphertexts(pub, b).to_device()
+    eng = pub._get_engine()
+    assert eng.lazy_products()
+    s = va + vb
+    assert s._debt == 1 and s.on_device
+    bad = adv.first_mismatch(s.ciphertexts(False), want, fam)
+    assert bad is None, "debt form: %s" % bad
+    assert eng.pair_form() or key_bits != 2048
+    if eng.pair_form():
+        sp = va.to_pair() + vb
+        assert sp._pair
+        bad = adv.first_mismatch(sp.ciphertexts(False), want, fam)
+        assert bad is None, "pair form: %s" % bad
+    # the tree of sum(): 64 leaves, rows i and i + 32 multiply first, then i and i + 16 of the results, ...
+    units = [t for t, f in zip(want, fam) if f in ("Z2", "Zall", "ZO", "O2", "NearZ") and math.gcd(t, n) == 1][:10]
+    t1 = units + [1, 2, N - 1, N - 2, N - 3, 3][:16 - len(units)]
+    assert len(t1) == 16
+    t2 = [pow(t, -1, N) if i % 2 == 0 else N - pow(t, -1, N) for i, t in enumerate(t1)]       # level two: 1, n^2 - 1, 1, ...
+    la, lb = adv.pairs_for(t1 + t2, N, rng, n_root=n)
+    leaves = la + lb
+    level1 = [x * y % N for x, y in zip(leaves[:32], leaves[32:])]
+    level2 = [x * y % N for x, y in zip(level1[:16], level1[16:])]
+    assert level1 == t1 + t2 and level2 == [1, N - 1] * 8
+    for vec in (leaves, a + b + leaves[:5]):                  # (the second: an odd count, rows left over on the way up)
+        root = 1
+        for x in vec:
+            root = root * x % N
+        total = EncryptedVector.from_ciphertexts(pub, vec).to_device().sum()
+        assert total.ciphertext(False) == root, "tree of %d leaves" % len(vec)
