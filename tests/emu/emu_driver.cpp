@@ -335,6 +335,10 @@ static void run_miller_rabin(MillerRabinArgs A) {
     }
 }
 static int g_prefer_group = 0;
+// what emu_encrypt / emu_powmod_n2 dispatched for their LAST subtraction: {kind, G, L, rows} (emu_exit_layout restates their decision
+// tree; tests compare the two after every call, so that the restatement cannot drift unnoticed)
+static int g_last_exit[4] = {-1, 0, 0, 0};
+static void note_exit(int kind, int G, int L, int rows) { g_last_exit[0] = kind; g_last_exit[1] = G; g_last_exit[2] = L; g_last_exit[3] = rows; }
 static int g_unit = 1;    // 1: the scaled-modulus path for r^n where the key offers it (the library's large-batch form)
 static int g_engine = 1;  // 1: split-modulus kernels where a geometry exists (the product default), 0: full-width only
 
@@ -586,6 +590,7 @@ int emu_encrypt(const uint32_t* n, int n_limbs, const uint32_t* m, const uint32_
             A.out = c_in ? power.data() : c_out; A.out_limbs = P.s2; A.batch = B;
             if (Q.scaled.G == 64) { DISPATCH_SPLIT(Q.scaled.G, Q.scaled.L, (run_split_late<GG, LL, kModeEncrypt>(A))); }
             else { DISPATCH_SPLIT(Q.scaled.G, Q.scaled.L, (run_split<GG, LL, kModeEncrypt, true>(A))); }   // 16 lanes: the quick form
+            note_exit(1, Q.scaled.G, Q.scaled.L, Q.scaled.rows);
             if (c_in) {
                 MulArgs Mu;
                 memset(&Mu, 0, sizeof Mu);
@@ -594,6 +599,7 @@ int emu_encrypt(const uint32_t* n, int n_limbs, const uint32_t* m, const uint32_
                 int MG, ML;
                 light_geometry_of(P.nsq, MG, ML);
                 DISPATCH_GL(MG, ML, (run_mul<GG, LL>(Mu)));
+                note_exit(0, MG, ML, MG * ML);
             }
             return 0;
         }
@@ -621,6 +627,7 @@ int emu_encrypt(const uint32_t* n, int n_limbs, const uint32_t* m, const uint32_
             int MG, ML;
             light_geometry_of(P.nsq, MG, ML);
             DISPATCH_GL(MG, ML, (run_mul<GG, LL>(Mu)));
+            note_exit(0, MG, ML, MG * ML);
             return 0;
         }
         if (g_engine && P.nsplit.G) {
@@ -639,10 +646,12 @@ int emu_encrypt(const uint32_t* n, int n_limbs, const uint32_t* m, const uint32_
                 A.base_chunks = chunks_for(P.s1, P.nquick.scaled.rows);
                 A.post_chunks = chunks_for(A.post_limbs, P.nquick.scaled.rows);
                 DISPATCH_AB(P.nquick.scaled.L, (run_split_ab<LL, kModeEncrypt>(A)));
+                note_exit(1, 64, P.nquick.scaled.L, P.nquick.scaled.rows);
                 return 0;
             }
             if (c_in) { DISPATCH_SPLIT(M.G, M.L, (run_split<GG, LL, kModeObfuscate>(A))); }
             else { DISPATCH_SPLIT(M.G, M.L, (run_split<GG, LL, kModeEncrypt>(A))); }
+            note_exit(1, M.G, M.L, M.rows);
             return 0;
         }
         UniformArgs A;
@@ -655,6 +664,44 @@ int emu_encrypt(const uint32_t* n, int n_limbs, const uint32_t* m, const uint32_
         A.out = c_out; A.out_limbs = P.s2; A.batch = B;
         if (c_in) { DISPATCH_GL(P.nsq.G, P.nsq.L, (run_uniform<GG, LL, kModeObfuscate>(A))); }
         else { DISPATCH_GL(P.nsq.G, P.nsq.L, (run_uniform<GG, LL, kModeEncrypt>(A))); }
+        note_exit(0, P.nsq.G, P.nsq.L, P.nsq.G * P.nsq.L);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// Where the LAST conditional subtraction of emu_encrypt (op 0), of its obfuscate form (op 1) and of emu_powmod_n2 (op 2) runs
+// under the present settings — the decision tree of those functions, nothing else: out = {kind, G, L, rows}.  kind 1: split_exit
+// (cond_sub_pair on n^2 = lo + hi * 2^(29 rows), each half on rows / L lanes of a group of G); kind 0: canonicalize on the G * L
+// limbs of n^2's full-width geometry (rows = G * L).  tests/lookahead.py lays its targets out on these lanes.
+void emu_last_exit(int* out) { for (int i = 0; i < 4; ++i) out[i] = g_last_exit[i]; }
+int emu_exit_layout(const uint32_t* n, int n_limbs, int op, int* out) {
+    try {
+        host::PublicPlan P = host::build_public(n, n_limbs, g_prefer_group);
+        const auto full = [&](int G, int L) { out[0] = 0; out[1] = G; out[2] = L; out[3] = G * L; };
+        const auto pair = [&](const host::SplitPack& M) { out[0] = 1; out[1] = M.G; out[2] = M.L; out[3] = M.rows; };
+        int MG, ML;
+        light_geometry_of(P.nsq, MG, ML);
+        if (op == 2) {
+            if (g_engine && P.nsplit.G == 64 && g_wave_pairs && P.nquick.ok()) pair(P.nquick.scaled);
+            else if (g_engine && P.nsplit.G) pair(P.nsplit);
+            else full(P.nsq.G, P.nsq.L);
+            return 0;
+        }
+        if (g_engine && g_late && !(P.nsplit.G == 64 && g_wave_pairs)) {
+            if (!(P.nsplit.G >= 16 && P.nquick.ok() && P.nquick.scaled.L <= 9)) throw std::invalid_argument("no late kernel for this key / group");
+            if (op == 1) full(MG, ML); else pair(P.nquick.scaled);
+        } else if (g_engine && g_unit && P.nunit.G) {
+            full(MG, ML);
+        } else if (g_engine && P.nsplit.G) {
+            if (op == 0 && P.nsplit.G == 64 && g_wave_pairs) {
+                if (!P.nquick.ok()) throw std::invalid_argument("no wave-pair constants for this key");
+                pair(P.nquick.scaled);
+            } else {
+                pair(P.nsplit);
+            }
+        } else {
+            full(P.nsq.G, P.nsq.L);
+        }
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
@@ -1053,6 +1100,7 @@ int emu_powmod_n2(const uint32_t* n, int n_limbs, const uint32_t* base, const ui
                     A.out = out + i * (uint64_t)P.s2; A.out_limbs = P.s2; A.batch = 1;
                     DISPATCH_AB(P.nquick.scaled.L, (run_split_ab<LL, kModeEncrypt>(A)));
                 }
+                note_exit(1, 64, P.nquick.scaled.L, P.nquick.scaled.rows);
                 return 0;
             }
         }
@@ -1067,6 +1115,7 @@ int emu_powmod_n2(const uint32_t* n, int n_limbs, const uint32_t* base, const ui
             A.n_windows = std::max(1, (max_bits + A.window - 1) / A.window);
             A.out = out; A.out_limbs = P.s2; A.batch = B;
             DISPATCH_SPLIT(M.G, M.L, (run_var_split<GG, LL>(A)));
+            note_exit(1, M.G, M.L, M.rows);
             return 0;
         }
         VarArgs A;
@@ -1076,6 +1125,7 @@ int emu_powmod_n2(const uint32_t* n, int n_limbs, const uint32_t* base, const ui
         A.n_windows = std::max(1, (max_bits + A.window - 1) / A.window);
         A.out = out; A.out_limbs = P.s2; A.batch = B;
         DISPATCH_GL(P.nsq.G, P.nsq.L, (run_var<GG, LL>(A)));
+        note_exit(0, P.nsq.G, P.nsq.L, P.nsq.G * P.nsq.L);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
@@ -1155,6 +1205,99 @@ int emu_miller_rabin(const uint32_t* n, const uint32_t* base, int limbs, uint8_t
         MillerRabinArgs A;
         A.n = n; A.base = base; A.limbs = limbs; A.pass = pass; A.batch = B;
         DISPATCH_GL(geo.G, geo.L, (run_miller_rabin<GG, LL>(A)));
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// ---- the way out of the lazily reduced form, one function at a time (tests/test_lookahead.py) --------------------------------
+// every (G, L) some kernel is compiled for: the full-width list and the split-modulus list together
+#define DISPATCH_LANES(G_, L_, CALL)                                                  \
+    switch ((G_) * 100 + (L_)) {                                                      \
+        case 118: { constexpr int GG = 1, LL = 18; CALL; break; }                     \
+        case 209: { constexpr int GG = 2, LL = 9; CALL; break; }                      \
+        case 218: { constexpr int GG = 2, LL = 18; CALL; break; }                     \
+        case 227: { constexpr int GG = 2, LL = 27; CALL; break; }                     \
+        case 236: { constexpr int GG = 2, LL = 36; CALL; break; }                     \
+        case 405: { constexpr int GG = 4, LL = 5; CALL; break; }                      \
+        case 409: { constexpr int GG = 4, LL = 9; CALL; break; }                      \
+        case 414: { constexpr int GG = 4, LL = 14; CALL; break; }                     \
+        case 418: { constexpr int GG = 4, LL = 18; CALL; break; }                     \
+        case 427: { constexpr int GG = 4, LL = 27; CALL; break; }                     \
+        case 436: { constexpr int GG = 4, LL = 36; CALL; break; }                     \
+        case 803: { constexpr int GG = 8, LL = 3; CALL; break; }                      \
+        case 805: { constexpr int GG = 8, LL = 5; CALL; break; }                      \
+        case 807: { constexpr int GG = 8, LL = 7; CALL; break; }                      \
+        case 809: { constexpr int GG = 8, LL = 9; CALL; break; }                      \
+        case 814: { constexpr int GG = 8, LL = 14; CALL; break; }                     \
+        case 818: { constexpr int GG = 8, LL = 18; CALL; break; }                     \
+        case 827: { constexpr int GG = 8, LL = 27; CALL; break; }                     \
+        case 1601: { constexpr int GG = 16, LL = 1; CALL; break; }                    \
+        case 1602: { constexpr int GG = 16, LL = 2; CALL; break; }                    \
+        case 1603: { constexpr int GG = 16, LL = 3; CALL; break; }                    \
+        case 1604: { constexpr int GG = 16, LL = 4; CALL; break; }                    \
+        case 1605: { constexpr int GG = 16, LL = 5; CALL; break; }                    \
+        case 1607: { constexpr int GG = 16, LL = 7; CALL; break; }                    \
+        case 1609: { constexpr int GG = 16, LL = 9; CALL; break; }                    \
+        case 1614: { constexpr int GG = 16, LL = 14; CALL; break; }                   \
+        case 1618: { constexpr int GG = 16, LL = 18; CALL; break; }                   \
+        case 6401: { constexpr int GG = 64, LL = 1; CALL; break; }                    \
+        case 6402: { constexpr int GG = 64, LL = 2; CALL; break; }                    \
+        case 6403: { constexpr int GG = 64, LL = 3; CALL; break; }                    \
+        case 6405: { constexpr int GG = 64, LL = 5; CALL; break; }                    \
+        default: throw std::invalid_argument("unsupported geometry");                 \
+    }
+
+// mont_core.h group_carry_in<G> on `count` pairs of ballots: cin[i] and out_top[i] as the device computes them
+int emu_group_carry_in(int G, const uint64_t* gen, const uint64_t* prop, uint64_t* cin, uint64_t* out_top, uint64_t count) {
+    for (uint64_t i = 0; i < count; ++i) {
+        switch (G) {
+            case 1: cin[i] = group_carry_in<1>(gen[i], prop[i], out_top[i]); break;
+            case 2: cin[i] = group_carry_in<2>(gen[i], prop[i], out_top[i]); break;
+            case 4: cin[i] = group_carry_in<4>(gen[i], prop[i], out_top[i]); break;
+            case 8: cin[i] = group_carry_in<8>(gen[i], prop[i], out_top[i]); break;
+            case 16: cin[i] = group_carry_in<16>(gen[i], prop[i], out_top[i]); break;
+            case 64: cin[i] = group_carry_in<64>(gen[i], prop[i], out_top[i]); break;
+            default: g_err = "unsupported group width"; return 1;
+        }
+    }
+    return 0;
+}
+
+// One lane-level function on `waves` wavefronts of GIVEN limbs.  A wave's operand is 64*L words of 29-bit limbs (almost-normalised
+// where the function takes that form): lane l holds words [l*L, (l+1)*L), so a wave is 64/G independent numbers of G*L limbs.
+//   op 0  normalize_full(t)          op 1  add_normalize(t, u)          op 2  cond_sub(t, u)          op 3  canonicalize(t, u)
+//   op 4  split_core.h cond_sub_pair: t and u hold (lo | hi) and (mlo | mhi), 2 * 64*L words per wave
+// u is given per lane like t (every group may have a modulus of its own).  out has the shape of t.
+int emu_lane_op(int G, int L, int op, const uint32_t* t, const uint32_t* u, uint32_t* out, int waves) {
+    try {
+        if (op < 0 || op > 4) throw std::invalid_argument("unknown lane op");
+        if (op != 0 && u == nullptr) throw std::invalid_argument("this lane op takes a second operand");
+        DISPATCH_LANES(G, L, ({
+            constexpr int W = 64 * LL;
+            const size_t stride = (size_t)(op == 4 ? 2 * W : W);
+            for (int w = 0; w < waves; ++w) {
+                const uint32_t* tw = t + (size_t)w * stride;
+                const uint32_t* uw = u ? u + (size_t)w * stride : nullptr;
+                uint32_t* ow = out + (size_t)w * stride;
+                wave::run_wave([&](uint32_t lane) {
+                    const Lanes<GG> ln(lane);
+                    uint32_t x[LL], y[LL], xh[LL], yh[LL];
+                    load_row<LL>(x, tw, lane);
+                    if (uw) load_row<LL>(y, uw, lane);
+                    if (op == 0) normalize_full<GG, LL>(x, ln);
+                    else if (op == 1) add_normalize<GG, LL>(x, y, ln);
+                    else if (op == 2) cond_sub<GG, LL>(x, y, ln);
+                    else if (op == 3) canonicalize<GG, LL>(x, y, ln);
+                    else {
+                        load_row<LL>(xh, tw + W, lane);
+                        load_row<LL>(yh, uw + W, lane);
+                        cond_sub_pair<GG, LL>(x, xh, y, yh, ln);
+                        store_row<LL>(ow + W, xh, lane);
+                    }
+                    store_row<LL>(ow, x, lane);
+                });
+            }
+        }));
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }

@@ -276,6 +276,42 @@ class Emu:
         self._ck(rc)
         return out.astype(bool)
 
+    def exit_layout(self, n, op):
+        """where the last conditional subtraction of 'encrypt' / 'obfuscate' / 'powmod' runs under the present settings:
+        (pair, G, L, rows) — pair: split_exit's cond_sub_pair (each half of n^2 on rows / L lanes), else canonicalize on G lanes"""
+        out = (ctypes.c_int * 4)()
+        self._ck(self.L.emu_exit_layout(P(n), n.shape[0], ("encrypt", "obfuscate", "powmod").index(op), out))
+        return bool(out[0]), out[1], out[2], out[3]
+
+    def last_exit(self):
+        """(pair, G, L, rows) the last encrypt / obfuscate / powmod_n2 call dispatched its last subtraction on"""
+        out = (ctypes.c_int * 4)()
+        self.L.emu_last_exit(out)
+        return bool(out[0]), out[1], out[2], out[3]
+
+    def group_carry_in(self, G, gen, prop):
+        """csrc/mont_core.h group_carry_in<G> on arrays of 64-bit ballots -> (cin, out_top)"""
+        gen = np.ascontiguousarray(gen, dtype=np.uint64)
+        prop = np.ascontiguousarray(prop, dtype=np.uint64)
+        cin, out_top = np.zeros_like(gen), np.zeros_like(gen)
+        self._ck(self.L.emu_group_carry_in(G, P(gen), P(prop), P(cin), P(out_top), ctypes.c_uint64(gen.shape[0])))
+        return cin, out_top
+
+    LANE_OPS = {"normalize_full": 0, "add_normalize": 1, "cond_sub": 2, "canonicalize": 3, "cond_sub_pair": 4}
+
+    def lane_op(self, G, L, op, t, u=None):
+        """one of LANE_OPS on given limbs: t (and u: the addend / the modulus, per group) are (waves, 64/G, G*L) arrays of 29-bit
+        limbs — (waves, 2, 64/G, G*L) for cond_sub_pair: low halves, then high halves.  Returns the function's result in t's shape."""
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        pair = op == "cond_sub_pair"
+        assert t.shape[1:] == ((2, 64 // G, G * L) if pair else (64 // G, G * L)), t.shape
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.uint32)
+            assert u.shape == t.shape
+        out = np.zeros_like(t)
+        self._ck(self.L.emu_lane_op(G, L, self.LANE_OPS[op], P(t), P(u) if u is not None else None, P(out), t.shape[0]))
+        return out
+
     def to_decimal(self, limbs, width=None):
         """csrc/radix_conv.h limbs_to_decimal per row -> (rows, width) uint8 ASCII digits, '0'-padded on the left"""
         limbs = np.ascontiguousarray(limbs, dtype=np.uint32)
