@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 6
+#define PHE_HIP_ABI_VERSION 7
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -266,6 +266,17 @@ int phe_hip_pair_multiexp_rows_dev(phe_hip_ctx* ctx, const uint32_t* pair_base, 
  * the reference is a chain of _raw_add (phe/paillier.py:705-719); the product of residues is independent of the order —
  * as a pairwise tree of log2(batch) launches queued back to back on `stream`, no host round trip between the levels. */
 int phe_hip_pair_reduce_dev(phe_hip_ctx* ctx, const uint32_t* pair, size_t batch, uint32_t* out, void* stream);
+/* Grouped homomorphic sums: out_pair[t] (one pair row per task) = the product of the rows of task t — per group the chain of
+ * _raw_add that summing its EncryptedNumbers is (phe/paillier.py:705-719; the product of residues is independent of the
+ * order) — at ONE pair product per input row: a limb group walks the rows of its task with the running product in registers
+ * (csrc/segment_core.h).  rows: n_rows pair rows (rows_are_pair != 0), or n_rows canonical residues of ct_limbs words, which
+ * are converted as they are read.  Task t covers the entries task_ptr[t] .. task_ptr[t+1] (tasks + 1 offsets, device) of
+ * idx (row numbers < n_rows, device), or — idx == NULL — the rows task_ptr[t] .. task_ptr[t+1] themselves (the partial
+ * products of an earlier call, reduced further).  order: the sequence in which the tasks are handed to the limb groups
+ * (longest first keeps the groups of a wavefront equally busy), or NULL.  An empty task yields the pair of 1.  The rows
+ * come out through phe_hip_from_pair_dev.  EINVAL without the split-modulus engine. */
+int phe_hip_segment_reduce_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, const uint64_t* task_ptr,
+                               const uint32_t* idx, const uint32_t* order, uint32_t* out_pair, size_t tasks, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

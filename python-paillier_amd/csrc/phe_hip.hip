@@ -30,6 +30,7 @@
 #include "wave_gfx950.h"
 #include "mont_core.h"
 #include "split_core.h"
+#include "segment_core.h"
 #include "mul_io.h"
 #include "mul_table.h"
 #include "decrypt_tail.h"
@@ -117,6 +118,12 @@ PHE_DECLARE_SPLIT_PART(s16c)
 PHE_DECLARE_SPLIT_PART(s64a)
 PHE_DECLARE_SPLIT_PART(s64b)
 #undef PHE_DECLARE_SPLIT_PART
+}  // namespace phe
+
+namespace phe {
+namespace seg {  // kernels_seg.hip
+int launch_segment_reduce(int G, int L, int blocks, hipStream_t st, const SegmentArgs& A);
+}  // namespace seg
 }  // namespace phe
 
 namespace phe {
@@ -2059,6 +2066,39 @@ int phe_hip_pair_reduce_dev(phe_hip_ctx* ctx, const uint32_t* pair, size_t batch
         }
     }
     HIP_TRY(hipMemcpyAsync(out, P, w * 4, hipMemcpyDeviceToDevice, st));
+    return PHE_HIP_OK;
+}
+
+// out_pair[t] = the product of the rows of task t (segment_core.h): grouped sums — one chain of _raw_add per group
+// (phe/paillier.py:705-719) — at one pair product per input row.  The geometry is the pair rung of `tasks` limb groups.
+int phe_hip_segment_reduce_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, const uint64_t* task_ptr,
+                               const uint32_t* idx, const uint32_t* order, uint32_t* out_pair, size_t tasks, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (tasks == 0) return PHE_HIP_OK;
+    if (!task_ptr || !out_pair || (n_rows && !rows)) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (n_rows > 0xFFFFFFFFull) return fail(PHE_HIP_EINVAL, "row numbers are 32-bit");
+    if (int rc = bind_device(ctx)) return rc;
+    if (!(ctx->use_split && ctx->d_nsplit.G)) return fail(PHE_HIP_EINVAL, "the pair form needs the split-modulus engine");
+    PHE_CTX_ORDER(ctx, stream);
+    const DevSplit& sp = pick_pair_split(ctx, tasks);
+    SegmentArgs A;
+    A.mod = sp.c;
+    A.rows = rows;
+    A.rows_are_pair = rows_are_pair ? 1 : 0;
+    A.limbs = ctx->pub.s2;
+    A.chunks = chunks_for(ctx->pub.s2, sp.rows);
+    A.n_rows = n_rows;
+    A.task_ptr = task_ptr;
+    A.idx = idx;
+    A.order = order;
+    A.out = out_pair;
+    A.tasks = tasks;
+    ctx->last_path = 0;
+    ctx->last_geom_pub = geom_code(sp.G, sp.L);
+    const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
+    if (phe::seg::launch_segment_reduce(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+    HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;
 }
 

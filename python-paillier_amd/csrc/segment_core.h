@@ -1,0 +1,86 @@
+// segment_core.h — grouped homomorphic sums: out[task] = the product of a RUN of ciphertext rows, in the pair form.
+// Summing ciphertexts by group (gradient histograms of federated boosting, per-class aggregation, group-by) is a chain of
+// EncryptedNumber.__add__ = _raw_add per group (phe/paillier.py:705-719: mulmod(a, b, n^2)); the product of residues does not
+// depend on the order.  On rows in the pair form (split_core.h "resident ciphertext rows") one addition is ONE pair product, and a
+// limb group that walks the rows of its segment keeps the running product in registers: one split_mul per input row (plus one
+// split_conv where the rows arrive as 32-bit-word residues), nothing stored but the segment's product.
+//
+// One limb group owns one TASK: the run idx[first .. first + count) of row numbers (idx == nullptr: the rows first .. first + count
+// themselves — the partial products of an earlier level).  The host cuts long segments into tasks of bounded length and reduces
+// the partials by further levels of the same kernel (phe/_engine.py segment_reduce_dev), so that a wavefront's groups carry
+// similar loads; `order` hands the tasks out longest first, as multiexp_lookup_body takes its rows.
+//
+// The groups of a wavefront run the loop to the wavefront's LONGEST task: split_mul and split_conv move operands between the
+// lanes and through the group's LDS row in lock step, so a group that has run out of rows (or a slot past the last task) still
+// executes every product of the wave — by the pair of 1 (mod.e), which leaves the value of its accumulator as it is — reads a
+// valid address (row 0) where the wave converts residues, and stores nothing for a slot past the end.
+#pragma once
+
+namespace phe {
+
+struct SegmentArgs {
+    SplitConsts mod;
+    const uint32_t* rows;      // rows_are_pair: (n_rows, 2H) pair rows; else (n_rows, limbs) canonical residues in 32-bit words
+    int rows_are_pair;         // (the launcher picks segment_reduce_body<G, L, PAIR> by it)
+    int limbs;                 // 32-bit words of a residue row
+    int chunks;                // ceil(32*limbs / (29 rows))
+    uint64_t n_rows;           // > 0 whenever a task has rows; every row number is clamped below it
+    const uint64_t* task_ptr;  // (tasks + 1) offsets into idx (or into the rows themselves when idx == nullptr)
+    const uint32_t* idx;       // row number of every entry, or nullptr
+    const uint32_t* order;     // (tasks) visiting order, or nullptr
+    uint32_t* out;             // (tasks, 2H) pair rows: out[t] = prod of task t's rows; the pair of 1 for an empty task
+    uint64_t tasks;            // > 0
+};
+
+// PAIR: the rows are pair rows (A.rows_are_pair, which the launcher turns into this compile-time switch: the loop over pair rows
+// keeps the registers of pair_mul_body, the one over residues those of split_conv beside the running product)
+template <int G, int L, bool PAIR>
+PHE_DEV void segment_reduce_body(const SegmentArgs& A, uint32_t* lds_row, uint32_t slot, uint32_t total_slots, uint32_t lane) {
+    constexpr int H = G * L, S2 = 2 * H;
+    const Lanes<G> ln(lane);
+    const uint32_t g = ln.g;
+    SplitLane<G, L> K;
+    load_row<L>(K.n, A.mod.n, g);
+    K.n0inv = A.mod.n0inv;
+    K.rows_ = A.mod.rows;
+    K.row_a = lds_row;
+    K.row_c = lds_row + H;
+    const uint64_t n_iter = (A.tasks + total_slots - 1) / total_slots;
+    for (uint64_t it = 0; it < n_iter; ++it) {
+        uint64_t pos = slot + it * (uint64_t)total_slots;
+        const bool live = pos < A.tasks;
+        if (!live) pos = A.tasks - 1;
+        const uint64_t t = A.order ? (uint64_t)A.order[pos] : pos;
+        const uint64_t first = A.task_ptr[t];
+        const uint64_t count = (live && A.n_rows) ? A.task_ptr[t + 1] - first : 0;
+        uint32_t X0[L], X1[L], Y0[L], Y1[L];
+        load_row<L>(X0, wave::reread_ptr(A.mod.e), g);
+        load_row<L>(X1, wave::reread_ptr(A.mod.e) + H, g);
+        for (uint64_t el = 0; wave::ballot(el < count) != 0; ++el) {  // to the wavefront's longest task
+            const bool mine = el < count;
+            uint64_t r = 0;
+            if (mine) {
+                r = A.idx ? (uint64_t)A.idx[first + el] : first + el;
+                r = r < A.n_rows ? r : A.n_rows - 1;
+            }
+            if constexpr (PAIR) {
+                const uint32_t* src = mine ? A.rows + r * (uint64_t)S2 : A.mod.e;
+                load_row<L>(Y0, src, g);
+                load_row<L>(Y1, src + H, g);
+            } else {
+                split_conv<G, L>(Y0, Y1, A.rows + r * (uint64_t)A.limbs, A.limbs, A.chunks, A.mod, K, ln);
+                if (!mine) {
+                    load_row<L>(Y0, wave::reread_ptr(A.mod.e), g);
+                    load_row<L>(Y1, wave::reread_ptr(A.mod.e) + H, g);
+                }
+            }
+            split_mul<G, L>(X0, X1, Y0, Y1, K, ln);
+        }
+        if (live) {
+            store_row<L>(A.out + t * (uint64_t)S2, X0, g);
+            store_row<L>(A.out + t * (uint64_t)S2 + H, X1, g);
+        }
+    }
+}
+
+}  // namespace phe

@@ -146,6 +146,62 @@ class ObfuscatorPool:
             return parts
 
 
+# ---- grouped sums (EncryptedVector.segment_sum; csrc/segment_core.h) ------------------------------------------------------
+# One limb group multiplies the rows of one TASK; a segment longer than this is cut into tasks of (almost) equal length, and
+# the partial products are reduced by further levels of the same kernel.  Short tasks fill the GPU when the segments are few
+# and keep the groups of a wavefront in step; long ones leave fewer partials to store and read again.  Measured with
+# tools/bench_segment_sum.py (profiles/r08_segment_sum.json: 2048-bit key, 2^20 rows, 256 segments, kernels alone), caps
+# 8 / 16 / 32 / 64 / 128 / 256: 203 / 196 / 174 / 125 / 120 / 104 M rows/s on residues, 637 / 638 / 570 / 399 / 404 / 378 M rows/s
+# on pair rows.  8 and 16 tie within the spread of the repeats; 16 makes one level less.
+SEGMENT_TASK_ROWS = 16
+
+
+def _ranges(counts):
+    """0 .. c-1 for every c of counts, concatenated"""
+    counts = np.asarray(counts, dtype=np.int64)
+    total = int(counts.sum())
+    return np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(counts) - counts, counts)
+
+
+class SegmentPlan:
+    """What Engine.segment_reduce_dev launches: `levels` is a list of (task_ptr uint64 (tasks + 1), idx uint32 or None, order
+    uint32 (tasks)); level 0 reads the vector's rows through idx, every later level reads the partial products of the level
+    before (idx None: task t covers the partials task_ptr[t] .. task_ptr[t + 1]).  The last level has one task per segment."""
+
+    def __init__(self, levels, n_out):
+        self.levels, self.n_out = levels, n_out
+
+
+def plan_segments(seg_ids, n_segments, cap=None):
+    """seg_ids: (rows,) integers in [-1, n_segments) — -1 leaves the row out — or (F, rows): F groupings of the same rows, whose
+    segment s of grouping f is output row f * n_segments + s.  Pure numpy; the ids are taken as valid."""
+    cap = int(SEGMENT_TASK_ROWS if cap is None else cap)
+    if cap < 2:
+        raise ValueError("a task must be allowed at least two rows")
+    ids = np.asarray(seg_ids, dtype=np.int64)
+    if ids.ndim == 1:
+        ids = ids[None, :]
+    f, n = ids.shape
+    n_out = f * int(n_segments)
+    keep = ids >= 0
+    group = (ids + np.arange(f, dtype=np.int64)[:, None] * int(n_segments))[keep]
+    rows = np.broadcast_to(np.arange(n, dtype=np.int64), ids.shape)[keep]
+    key = group.astype(np.uint16) if n_out <= 1 << 16 else group              # (16-bit keys: numpy sorts them by radix)
+    idx = rows[np.argsort(key, kind="stable")].astype(np.uint32)             # the members of segment 0, of segment 1, ...
+    counts = np.bincount(group, minlength=n_out).astype(np.int64) if n_out else np.zeros(0, np.int64)
+    levels = []
+    while True:
+        per = np.maximum(1, -(-counts // cap))                                # tasks of every segment (an empty one: one empty task)
+        seg = np.repeat(np.arange(n_out, dtype=np.int64), per)
+        starts = (np.cumsum(counts) - counts)[seg] + (_ranges(per) * counts[seg]) // per[seg]
+        task_ptr = np.append(starts, counts.sum()).astype(np.uint64)          # tasks are contiguous: each ends where the next starts
+        order = np.argsort(-np.diff(task_ptr.astype(np.int64)), kind="stable").astype(np.uint32)
+        levels.append((task_ptr, idx if not levels else None, order))
+        if n_out == 0 or int(per.max()) <= 1:
+            return SegmentPlan(levels, n_out)
+        counts = per
+
+
 # Every public Engine method runs under the engine's re-entrant lock (see _native.serialised).  A key's engine owns
 # shared state: the obfuscator pool, whose entries must never be handed out twice (two ciphertexts sharing r^n reveal
 # m1 - m2), the host staging buffers, the native context's window tables and launch stream.
@@ -730,6 +786,46 @@ class Engine:
         self.ctx.pair_reduce_dev(pair.ptr, pair.rows, out.ptr)
         self.ctx.sync()
         return out
+
+    # ---- grouped sums on resident rows (include/phe_hip.h phe_hip_segment_reduce_dev) ------------------------------------
+    def has_segment_reduce(self):
+        """True when grouped sums have their kernel: the pair form is offered and the backend has the entry point"""
+        return bool(self.pair_form()) and hasattr(self.ctx, "segment_reduce_dev")
+
+    def segment_reduce_dev(self, store, is_pair, seg_ids, n_segments, want_pair=False):
+        """out[f * n_segments + s] = the product of the rows i of `store` with seg_ids[f][i] == s (plan_segments): per segment the
+        chain of _raw_add (phe/paillier.py:705-719) that summing its members is.  store: resident rows, pair form (is_pair) or
+        canonical residues; returns a DeviceArray of canonical residues, or of pair rows (want_pair).  Every level's index arrays
+        are uploaded before the first launch; the levels are queued back to back and waited for once."""
+        plan = plan_segments(seg_ids, n_segments, SEGMENT_TASK_ROWS)
+        if plan.n_out == 0:
+            return DeviceArray(self.ctx, 0, self.pair_form() if want_pair else self.ct_limbs)
+        return self.segment_launch_dev(store, is_pair, plan, self.segment_upload(plan), want_pair)
+
+    def segment_upload(self, plan):
+        """the index arrays of every level of a SegmentPlan as device blocks: [(task_ptr, idx or None, order), ...]"""
+        return [(DeviceArray.from_host(self.ctx, task_ptr.view(np.uint32).reshape(-1, 2)),
+                 DeviceArray.from_host(self.ctx, idx) if idx is not None else None,
+                 DeviceArray.from_host(self.ctx, order)) for task_ptr, idx, order in plan.levels]
+
+    def segment_launch_dev(self, store, is_pair, plan, dev, want_pair=False):
+        """the levels of an uploaded plan (segment_upload) over `store`, queued back to back; one synchronisation"""
+        words = self.pair_form()
+        if not is_pair and len(plan.levels[0][1]) > store.rows > 0:
+            store, is_pair = self.to_pair_dev(store), True   # several groupings read every row: into the form once, not F times
+        keep = [store]                                       # operands stay alive until the final synchronisation
+        rows, rows_are_pair, n_rows = store, is_pair, store.rows
+        for (_, _, order), (tp_d, idx_d, order_d) in zip(plan.levels, dev):
+            tasks = len(order)
+            out = DeviceArray(self.ctx, tasks, words)
+            self.ctx.segment_reduce_dev(rows.ptr, rows_are_pair, n_rows, tp_d.ptr, idx_d.ptr if idx_d is not None else None,
+                                        order_d.ptr, out.ptr, tasks)
+            keep.append(out)
+            rows, rows_are_pair, n_rows = out, True, tasks
+        if want_pair:
+            self.ctx.sync()
+            return rows
+        return self.from_pair_dev(rows)                      # (synchronises)
 
     def obfuscate_fresh_dev(self, c, rows=None):
         """obfuscate_dev with freshly drawn obfuscators, chunked like raw_encrypt_fresh (draw and upload of the next

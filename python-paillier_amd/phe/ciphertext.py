@@ -11,7 +11,7 @@ kernel launch each over the whole vector, with the same per-element semantics as
 import numpy as np
 
 from ._device import DeviceArray
-from ._engine import random_lt_n, random_lt_n_limbs
+from ._engine import _ranges, random_lt_n, random_lt_n_limbs
 from .codec import EncodedNumber
 
 
@@ -589,6 +589,97 @@ class EncryptedVector(object):
             merged = eng.raw_add(np.ascontiguousarray(limbs[:half]), np.ascontiguousarray(limbs[half:2 * half]))
             limbs = np.concatenate([merged, limbs[2 * half:]]) if limbs.shape[0] % 2 else merged
         return EncryptedNumber(pk, eng.to_ints(limbs)[0], exp)
+
+    def segment_sum(self, segment_ids, num_segments=None):
+        """Homomorphic sums BY GROUP -> EncryptedVector of `num_segments` rows: row s is the sum of the elements i with
+        segment_ids[i] == s — np.bincount(segment_ids, weights=x) on ciphertexts; the gradient histograms of federated
+        boosting, per-class aggregation, group-by.  segment_ids: len(self) integers in any order, -1 leaves an element out,
+        anything else outside [0, num_segments) raises ValueError; num_segments defaults to max + 1.  With segment_ids of
+        shape (F, len(self)) — F groupings of the same elements, one per feature — the result has F * num_segments rows, row
+        f * num_segments + s, and the vector enters the engine's form once, not F times.
+        The vector is aligned to its smallest exponent first, as sum() does, and every output row carries that exponent.
+        Row s is the canonical residue prod c_i mod n^2 over the aligned members: bit for bit what
+        `self.decrease_exponent_to(min)[members].sum()` and the reference's chain of `+` (EncryptedNumber._raw_add,
+        phe/paillier.py:705-719) return; a segment without members is the ciphertext 1 (an encryption of 0), as in matvec.
+        One limb group walks the rows of a segment with the running product in registers (Engine.segment_reduce_dev): one
+        pair product per element.  A resident vector gives a resident result (in the pair form if the vector is in it); a
+        host vector goes up, through the same kernel, and back.  Without that kernel (no split-modulus engine for the key
+        width) the sums are formed by rounds of element-wise products over the gathered halves of every group: same bits."""
+        pk = self.public_key
+        ids = np.asarray(segment_ids)
+        if ids.size == 0:
+            ids = ids.astype(np.int64)
+        if ids.dtype.kind not in "iu":
+            raise TypeError("segment_ids must be integers")
+        if ids.ndim not in (1, 2) or ids.shape[-1] != len(self):
+            raise ValueError("segment_ids must have shape (%d,) or (F, %d)" % (len(self), len(self)))
+        ids = ids.astype(np.int64)
+        if num_segments is None:
+            num_segments = int(ids.max()) + 1 if ids.size else 0
+        num_segments = int(num_segments)
+        if num_segments < 0:
+            raise ValueError("num_segments must not be negative")
+        bad = np.nonzero((ids.ravel() < -1) | (ids.ravel() >= num_segments))[0]
+        if len(bad):
+            raise ValueError("segment id %d is outside [0, %d) and is not -1" % (int(ids.ravel()[bad[0]]), num_segments))
+        n_out = (ids.shape[0] if ids.ndim == 2 else 1) * num_segments
+        eng = self._eng()
+        exp = int(self._exps.min()) if len(self) else 0
+        cur = self.decrease_exponent_to(exp) if len(self) else self
+        exps = np.full(n_out, exp, dtype=np.int64)
+        if eng.has_segment_reduce():
+            if self.on_device:
+                store = cur._store if cur._pair else cur._plain_rows()
+                out = eng.segment_reduce_dev(store, cur._pair, ids, num_segments, want_pair=self._pair)
+                return EncryptedVector(pk, out, exps, _pair=self._pair)
+            out = eng.segment_reduce_dev(eng.upload_cipher(cur._limbs), False, ids, num_segments)
+            return EncryptedVector(pk, out.to_host(), exps)
+        # rounds of the element-wise product: every group's members gathered side by side, its first half times its second
+        # half (an odd member carried), until one row per group is left
+        ids2 = ids[None, :] if ids.ndim == 1 else ids
+        keep = ids2 >= 0
+        group = (ids2 + np.arange(ids2.shape[0], dtype=np.int64)[:, None] * num_segments)[keep]
+        rows = np.broadcast_to(np.arange(len(self), dtype=np.int64), ids2.shape)[keep]
+        sel = rows[np.argsort(group, kind="stable")]
+        counts = np.bincount(group, minlength=n_out).astype(np.int64) if n_out else np.zeros(0, np.int64)
+        limbs = cur._plain_rows() if self.on_device else cur._limbs
+        gather = (lambda a, i: self._gather_dev(eng, a, i)) if self.on_device else (lambda a, i: np.ascontiguousarray(a[i]))
+        mul = eng.raw_add_dev if self.on_device else eng.raw_add
+        limbs = gather(limbs, sel)
+        while len(counts) and int(counts.max()) > 1:
+            half = counts // 2
+            a_idx = np.repeat(np.cumsum(counts) - counts, half) + _ranges(half)
+            prod = mul(gather(limbs, a_idx), gather(limbs, a_idx + np.repeat(half, half)))
+            n_prod = len(a_idx)
+            new_counts = half + (counts & 1)
+            take = np.empty(int(new_counts.sum()), dtype=np.int64)
+            new_start = np.cumsum(new_counts) - new_counts
+            take[np.repeat(new_start, half) + _ranges(half)] = np.arange(n_prod)
+            odd = np.nonzero(counts & 1)[0]
+            take[new_start[odd] + half[odd]] = n_prod + (np.cumsum(counts) - counts)[odd] + 2 * half[odd]
+            if self.on_device:
+                both = DeviceArray(eng.ctx, n_prod + limbs.rows, eng.ct_limbs)
+                eng.ctx.d2d(both.ptr, prod.ptr, prod.nbytes)
+                if limbs.nbytes:
+                    eng.ctx.d2d(both.ptr + prod.nbytes, limbs.ptr, limbs.nbytes)
+                eng.ctx.sync()
+            else:
+                both = np.concatenate([prod, limbs])
+            limbs, counts = gather(both, take), new_counts
+        host = limbs.to_host() if self.on_device else limbs
+        out = np.zeros((n_out, eng.ct_limbs), dtype=np.uint32)
+        out[:, 0] = 1                                              # a group without members: the ciphertext 1
+        out[np.nonzero(counts)[0]] = host
+        return EncryptedVector(pk, eng.upload_cipher(out) if self.on_device else out, exps)
+
+    @staticmethod
+    def _gather_dev(eng, rows, index):
+        idx = DeviceArray.from_host(eng.ctx, np.asarray(index, dtype=np.uint32))
+        out = DeviceArray(eng.ctx, len(index), eng.ct_limbs)
+        if len(index):
+            eng.ctx.gather_rows_dev(rows.ptr, rows.rows, idx.ptr, out.ptr, eng.ct_limbs, len(index))
+            eng.ctx.sync()
+        return out
 
     # ---- bulk wire format (docs/serialisation.rst:24-43 of the reference) ----------------------------------
     def to_json(self, be_secure=True):
