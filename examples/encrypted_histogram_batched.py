@@ -12,6 +12,11 @@ histograms back.  With the reference that is one chain of EncryptedNumber `+` pe
 i.e. one limb group per (feature, bin) walks its samples with the running product in registers: one pair product per
 sample and feature.  The label holder decrypts the histograms; they equal np.bincount on the plaintext gradients.
 
+A split at threshold b sends the bins 0 .. b to the left child, so what the label holder scores is, per feature, the RUNNING
+sum over the bins — which the feature holder can form on the ciphertexts as well, before they go back:
+
+    left = hist.cumsum(block=n_bins)                    # per feature: sum of the gradients left of every threshold
+
 python examples/encrypted_histogram_batched.py [key_length] [samples] [features] [bins]
 """
 import os
@@ -47,9 +52,13 @@ def run(key_length=1024, n_samples=2048, n_features=4, n_bins=16, device=None, v
     t2 = time.perf_counter()
     hist = np.array(privkey.decrypt_batch(enc_hist)).reshape(n_features, n_bins)     # label holder, one launch
     t3 = time.perf_counter()
+    enc_left = enc_hist.cumsum(block=n_bins)                                    # feature holder: left-child sums of every threshold
+    t4 = time.perf_counter()
+    left = np.array(privkey.decrypt_batch(enc_left)).reshape(n_features, n_bins)
 
     clear = np.stack([np.bincount(b[in_node], weights=gradients[in_node], minlength=n_bins) for b in bins])
     err = float(np.max(np.abs(hist - clear)))
+    err_left = float(np.max(np.abs(left - np.cumsum(clear, axis=1))))
     if verbose:
         print("key %d bits, %d samples (%d in the node), %d features x %d bins" % (key_length, n_samples, in_node.sum(), n_features, n_bins))
         print("encrypt the gradients:        %.3f s" % (t1 - t0))
@@ -57,7 +66,10 @@ def run(key_length=1024, n_samples=2048, n_features=4, n_bins=16, device=None, v
               % (t2 - t1, n_features * in_node.sum() / (t2 - t1)))
         print("decrypt the histograms:       %.3f s" % (t3 - t2))
         print("max |histogram - np.bincount| %.3e" % err)
+        print("encrypted left-child sums:    %.3f s  (cumsum over the %d bins of every feature)" % (t4 - t3, n_bins))
+        print("max |left sums - np.cumsum|   %.3e" % err_left)
     assert err < 1e-9, err
+    assert err_left < 1e-9, err_left
     return hist, clear
 
 

@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 7
+#define PHE_HIP_ABI_VERSION 8
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -277,6 +277,19 @@ int phe_hip_pair_reduce_dev(phe_hip_ctx* ctx, const uint32_t* pair, size_t batch
  * come out through phe_hip_from_pair_dev.  EINVAL without the split-modulus engine. */
 int phe_hip_segment_reduce_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, const uint64_t* task_ptr,
                                const uint32_t* idx, const uint32_t* order, uint32_t* out_pair, size_t tasks, void* stream);
+/* Running homomorphic sums: out_pair[i] (n_rows pair rows) = the carry of the task that owns row i times the product of that
+ * task's rows up to and including i — every prefix of the chain of _raw_add (phe/paillier.py:705-719) that adding
+ * EncryptedNumbers one after the other is, kept instead of thrown away — at ONE pair product per row: the walk of
+ * phe_hip_segment_reduce_dev that stores after every product (csrc/segment_core.h segment_scan_body).  rows: as there.  Task t
+ * owns the CONSECUTIVE rows task_ptr[t] .. task_ptr[t+1] (tasks + 1 offsets, device; what lies at or beyond n_rows is
+ * ignored).  carry_idx (tasks numbers, device): the row of carry_pair (tasks pair rows, device: numbers at or above `tasks`
+ * are clamped) that task t starts from, 0xFFFFFFFF for none; carry_idx == NULL or carry_pair == NULL: every task starts
+ * from 1.  carry_idx without carry_pair is EINVAL.  Rows that no task owns are left as they are.  Nothing passes between
+ * workgroups: the carries come from earlier calls (the tasks' totals by phe_hip_segment_reduce_dev over the same task_ptr with
+ * idx == NULL, scanned by this call; phe/_engine.py plan_scan).  EINVAL without the split-modulus engine. */
+int phe_hip_segment_scan_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows,
+                             const uint64_t* task_ptr, const uint32_t* carry_pair, const uint32_t* carry_idx,
+                             uint32_t* out_pair, size_t tasks, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

@@ -123,6 +123,7 @@ PHE_DECLARE_SPLIT_PART(s64b)
 namespace phe {
 namespace seg {  // kernels_seg.hip
 int launch_segment_reduce(int G, int L, int blocks, hipStream_t st, const SegmentArgs& A);
+int launch_segment_scan(int G, int L, int blocks, hipStream_t st, const ScanArgs& A);
 }  // namespace seg
 }  // namespace phe
 
@@ -2097,6 +2098,41 @@ int phe_hip_segment_reduce_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_
     ctx->last_geom_pub = geom_code(sp.G, sp.L);
     const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
     if (phe::seg::launch_segment_reduce(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// out_pair[row] = carry of the row's task times the product of the task's rows up to and including it (segment_core.h
+// segment_scan_body): running sums — every prefix of a chain of _raw_add (phe/paillier.py:705-719) — at one pair product per
+// row.  The geometry is the pair rung of `tasks` limb groups.
+int phe_hip_segment_scan_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, const uint64_t* task_ptr,
+                             const uint32_t* carry_pair, const uint32_t* carry_idx, uint32_t* out_pair, size_t tasks, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (tasks == 0) return PHE_HIP_OK;
+    if (!task_ptr || !out_pair || (n_rows && !rows)) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (carry_idx && !carry_pair) return fail(PHE_HIP_EINVAL, "carry numbers without carry rows");
+    if (n_rows > 0xFFFFFFFFull || tasks > 0xFFFFFFFFull) return fail(PHE_HIP_EINVAL, "row numbers are 32-bit");
+    if (int rc = bind_device(ctx)) return rc;
+    if (!(ctx->use_split && ctx->d_nsplit.G)) return fail(PHE_HIP_EINVAL, "the pair form needs the split-modulus engine");
+    PHE_CTX_ORDER(ctx, stream);
+    const DevSplit& sp = pick_pair_split(ctx, tasks);
+    ScanArgs A;
+    A.mod = sp.c;
+    A.rows = rows;
+    A.rows_are_pair = rows_are_pair ? 1 : 0;
+    A.limbs = ctx->pub.s2;
+    A.chunks = chunks_for(ctx->pub.s2, sp.rows);
+    A.n_rows = n_rows;
+    A.task_ptr = task_ptr;
+    A.carry = carry_pair;
+    A.carry_idx = carry_idx;
+    A.out = out_pair;
+    A.tasks = tasks;
+    ctx->last_path = 0;
+    ctx->last_geom_pub = geom_code(sp.G, sp.L);
+    const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
+    if (phe::seg::launch_segment_scan(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
         return fail(PHE_HIP_EINVAL, "unsupported split geometry");
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;

@@ -83,4 +83,78 @@ PHE_DEV void segment_reduce_body(const SegmentArgs& A, uint32_t* lds_row, uint32
     }
 }
 
+// ---- running sums: out[row] = the product of the rows of its task up to and including `row`, times the task's carry ------------
+// A cumulative sum of ciphertexts (EncryptedVector.cumsum) is the same chain of _raw_add with every prefix kept: the walk of
+// segment_reduce_body that STORES AFTER EVERY PRODUCT and STARTS FROM A CARRY.  Task t owns the consecutive rows
+// task_ptr[t] .. task_ptr[t + 1] (the host cuts every sequence into tasks of near-equal length: no idx, no order); its carry —
+// the product of everything before the task in its sequence — was made by an earlier launch (phe/_engine.py plan_scan: the
+// tasks' totals by segment_reduce_body, scanned in turn).  Nothing passes between workgroups inside the kernel.
+struct ScanArgs {
+    SplitConsts mod;
+    const uint32_t* rows;       // rows_are_pair: (n_rows, 2H) pair rows; else (n_rows, limbs) canonical residues in 32-bit words
+    int rows_are_pair;          // (the launcher picks segment_scan_body<G, L, PAIR> by it)
+    int limbs;                  // 32-bit words of a residue row
+    int chunks;                 // ceil(32*limbs / (29 rows))
+    uint64_t n_rows;            // rows of `rows` and of `out`: a row number at or above it is neither read nor stored
+    const uint64_t* task_ptr;   // (tasks + 1) offsets: task t owns the rows task_ptr[t] .. task_ptr[t + 1]
+    const uint32_t* carry;      // (tasks, 2H) pair rows, or nullptr
+    const uint32_t* carry_idx;  // (tasks) row of `carry` a task starts from (< tasks), 0xFFFFFFFF: from 1; or nullptr
+    uint32_t* out;              // (n_rows, 2H) pair rows; a row that no task owns is left as it is
+    uint64_t tasks;             // > 0
+};
+
+constexpr uint32_t kScanNoCarry = 0xFFFFFFFFu;
+
+// The lock-step rules are those of segment_reduce_body: to the wavefront's longest task, a group that has run out multiplying
+// by the pair of 1 from a valid address and storing nothing.
+template <int G, int L, bool PAIR>
+PHE_DEV void segment_scan_body(const ScanArgs& A, uint32_t* lds_row, uint32_t slot, uint32_t total_slots, uint32_t lane) {
+    constexpr int H = G * L, S2 = 2 * H;
+    const Lanes<G> ln(lane);
+    const uint32_t g = ln.g;
+    SplitLane<G, L> K;
+    load_row<L>(K.n, A.mod.n, g);
+    K.n0inv = A.mod.n0inv;
+    K.rows_ = A.mod.rows;
+    K.row_a = lds_row;
+    K.row_c = lds_row + H;
+    const uint64_t n_iter = (A.tasks + total_slots - 1) / total_slots;
+    for (uint64_t it = 0; it < n_iter; ++it) {
+        uint64_t t = slot + it * (uint64_t)total_slots;
+        const bool live = t < A.tasks;
+        if (!live) t = A.tasks - 1;
+        const uint64_t first = A.task_ptr[t];
+        const uint64_t last = A.task_ptr[t + 1] < A.n_rows ? A.task_ptr[t + 1] : A.n_rows;
+        const uint64_t count = (live && first < last) ? last - first : 0;
+        const uint32_t* start = wave::reread_ptr(A.mod.e);
+        if (live && A.carry && A.carry_idx) {
+            const uint32_t c = A.carry_idx[t];
+            if (c != kScanNoCarry) start = A.carry + (c < A.tasks ? (uint64_t)c : A.tasks - 1) * (uint64_t)S2;
+        }
+        uint32_t X0[L], X1[L], Y0[L], Y1[L];
+        load_row<L>(X0, start, g);
+        load_row<L>(X1, start + H, g);
+        for (uint64_t el = 0; wave::ballot(el < count) != 0; ++el) {  // to the wavefront's longest task
+            const bool mine = el < count;
+            const uint64_t r = mine ? first + el : 0;                // (< n_rows: count stops at it)
+            if constexpr (PAIR) {
+                const uint32_t* src = mine ? A.rows + r * (uint64_t)S2 : A.mod.e;
+                load_row<L>(Y0, src, g);
+                load_row<L>(Y1, src + H, g);
+            } else {
+                split_conv<G, L>(Y0, Y1, A.rows + r * (uint64_t)A.limbs, A.limbs, A.chunks, A.mod, K, ln);
+                if (!mine) {
+                    load_row<L>(Y0, wave::reread_ptr(A.mod.e), g);
+                    load_row<L>(Y1, wave::reread_ptr(A.mod.e) + H, g);
+                }
+            }
+            split_mul<G, L>(X0, X1, Y0, Y1, K, ln);
+            if (mine) {
+                store_row<L>(A.out + r * (uint64_t)S2, X0, g);
+                store_row<L>(A.out + r * (uint64_t)S2 + H, X1, g);
+            }
+        }
+    }
+}
+
 }  // namespace phe

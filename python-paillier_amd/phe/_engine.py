@@ -202,6 +202,54 @@ def plan_segments(seg_ids, n_segments, cap=None):
         counts = per
 
 
+# ---- running sums (EncryptedVector.cumsum; csrc/segment_core.h segment_scan_body) --------------------------------------------
+# One limb group walks the consecutive rows of one TASK and stores the running product after every row; a sequence longer than
+# this is cut into tasks of (almost) equal length, whose totals are reduced (segment_reduce_body), scanned in turn, and handed
+# to the tasks as carries.  Short tasks fill the GPU and keep the groups of a wavefront in step; long ones leave fewer totals
+# to reduce, store and scan again (1/cap of the rows per level).  Measured with tools/bench_cumsum.py
+# (profiles/r09_cumsum.json: 2048-bit key, 2^20 pair rows in and out, kernels alone), caps 8 / 16 / 32 / 64 / 128 / 256:
+# 315 / 300 / 275 / 211 / 173 / 101 M rows/s as one sequence (7 / 5 / 4 / 4 / 3 / 3 levels), 389 / 429 / 443 / 410 / 345 / 389
+# M rows/s as 4096 blocks of 256 (the last: one task per block, no carries).  The long sequence wants 8, the histogram form 32;
+# 16 is within 5 % of the best on either (the repeats spread by 2 - 6 %).
+SCAN_TASK_ROWS = 16
+SCAN_NO_CARRY = 0xFFFFFFFF
+
+
+class ScanPlan:
+    """What Engine.scan_launch_dev launches: `levels` is a list of (task_ptr uint64 (tasks + 1), carry_idx uint32 (tasks) or
+    None, n_rows, seq_len).  Level 0 covers the vector's rows, level k + 1 the totals of level k's tasks (one row per task).
+    Task t of a level owns the consecutive rows task_ptr[t] .. task_ptr[t + 1], all inside one sequence of seq_len rows;
+    carry_idx[t] is the row of the NEXT level's scan that holds the product of everything before the task in its sequence
+    (t - 1), or SCAN_NO_CARRY for the first task of a sequence.  The last level has one task per sequence and no carries."""
+
+    def __init__(self, levels, n_rows, block):
+        self.levels, self.n_rows, self.block = levels, n_rows, block
+
+
+def plan_scan(n_rows, block=None, cap=None):
+    """The levels of a running sum over n_rows rows as n_rows / block sequences of `block` rows each (None: one sequence).
+    Pure numpy; n_rows is taken to be a multiple of block."""
+    cap = int(SCAN_TASK_ROWS if cap is None else cap)
+    if cap < 2:
+        raise ValueError("a task must be allowed at least two rows")
+    n_rows = int(n_rows)
+    seq_len = max(1, n_rows if block is None else int(block))
+    n_seq = n_rows // seq_len
+    levels, rows = [], n_rows
+    while True:
+        per = -(-seq_len // cap)                                              # tasks of every sequence, of (almost) equal length
+        within = np.tile(np.arange(per, dtype=np.int64), n_seq)
+        starts = np.repeat(np.arange(n_seq, dtype=np.int64) * seq_len, per) + (within * seq_len) // per
+        task_ptr = np.append(starts, rows).astype(np.uint64)                  # tasks are contiguous: each ends where the next starts
+        carry_idx = None
+        if per > 1:
+            carry_idx = np.where(within == 0, SCAN_NO_CARRY, np.arange(len(within), dtype=np.int64) - 1).astype(np.uint32)
+        levels.append((task_ptr, carry_idx, rows, seq_len))
+        if per == 1:
+            return ScanPlan(levels, n_rows, seq_len)
+        rows, seq_len = n_seq * per, per
+
+
 # Every public Engine method runs under the engine's re-entrant lock (see _native.serialised).  A key's engine owns
 # shared state: the obfuscator pool, whose entries must never be handed out twice (two ciphertexts sharing r^n reveal
 # m1 - m2), the host staging buffers, the native context's window tables and launch stream.
@@ -826,6 +874,58 @@ class Engine:
             self.ctx.sync()
             return rows
         return self.from_pair_dev(rows)                      # (synchronises)
+
+    # ---- running sums on resident rows (include/phe_hip.h phe_hip_segment_scan_dev) --------------------------------------
+    def has_segment_scan(self):
+        """True when running sums have their kernel: the pair form is offered and the backend has both entry points"""
+        return self.has_segment_reduce() and hasattr(self.ctx, "segment_scan_dev")
+
+    def segment_scan_dev(self, store, is_pair, block=None, want_pair=False):
+        """out[i] = the product of the rows of `store` from the start of row i's sequence of `block` rows (None: of the vector)
+        up to and including i (plan_scan): every prefix of the chain of _raw_add (phe/paillier.py:705-719).  store: resident
+        rows, pair form (is_pair) or canonical residues; returns a DeviceArray of canonical residues, or of pair rows
+        (want_pair)."""
+        if store.rows == 0:
+            return DeviceArray(self.ctx, 0, self.pair_form() if want_pair else self.ct_limbs)
+        plan = plan_scan(store.rows, block, SCAN_TASK_ROWS)
+        return self.scan_launch_dev(store, is_pair, plan, self.scan_upload(plan), want_pair)
+
+    def scan_upload(self, plan):
+        """the index arrays of every level of a ScanPlan as device blocks: [(task_ptr, carry_idx or None), ...]"""
+        return [(DeviceArray.from_host(self.ctx, task_ptr.view(np.uint32).reshape(-1, 2)),
+                 DeviceArray.from_host(self.ctx, carry_idx) if carry_idx is not None else None)
+                for task_ptr, carry_idx, _, _ in plan.levels]
+
+    def scan_launch_dev(self, store, is_pair, plan, dev, want_pair=False):
+        """the launches of an uploaded plan (scan_upload) over `store`, queued back to back; one synchronisation.  Down the
+        levels the totals of every level's tasks (segment_reduce_dev, idx NULL, over the level's own task_ptr); the last
+        level — one task per sequence — is scanned without carries; then up again, every level scanned from the carries that
+        the scan of its totals is."""
+        words = self.pair_form()
+        if store.rows != plan.n_rows or store.cols != (words if is_pair else self.ct_limbs):
+            raise ValueError("the plan was made for %d rows, the store has %d rows of %d words" % (plan.n_rows, store.rows, store.cols))
+        if not is_pair and len(plan.levels) > 1:
+            store, is_pair = self.to_pair_dev(store), True   # the reduce and the scan both read every row: into the form once
+        keep = [store]                                       # operands stay alive until the final synchronisation
+        inputs = [(store, is_pair)]
+        for (task_ptr, _, n_rows, _), (tp_d, _) in zip(plan.levels[:-1], dev):
+            tasks = len(task_ptr) - 1
+            totals = DeviceArray(self.ctx, tasks, words)
+            rows, rows_are_pair = inputs[-1]
+            self.ctx.segment_reduce_dev(rows.ptr, rows_are_pair, n_rows, tp_d.ptr, None, None, totals.ptr, tasks)
+            keep.append(totals)
+            inputs.append((totals, True))
+        carry = None
+        for (task_ptr, carry_idx, n_rows, _), (tp_d, ci_d), (rows, rows_are_pair) in reversed(list(zip(plan.levels, dev, inputs))):
+            out = DeviceArray(self.ctx, n_rows, words)
+            self.ctx.segment_scan_dev(rows.ptr, rows_are_pair, n_rows, tp_d.ptr, carry.ptr if carry is not None else None,
+                                      ci_d.ptr if (ci_d is not None and carry is not None) else None, out.ptr, len(task_ptr) - 1)
+            keep.append(out)
+            carry = out
+        if want_pair:
+            self.ctx.sync()
+            return carry
+        return self.from_pair_dev(carry)                     # (synchronises)
 
     def obfuscate_fresh_dev(self, c, rows=None):
         """obfuscate_dev with freshly drawn obfuscators, chunked like raw_encrypt_fresh (draw and upload of the next

@@ -672,6 +672,67 @@ class EncryptedVector(object):
         out[np.nonzero(counts)[0]] = host
         return EncryptedVector(pk, eng.upload_cipher(out) if self.on_device else out, exps)
 
+    def cumsum(self, block=None):
+        """Running homomorphic sums -> EncryptedVector of len(self) rows: row i is the sum of the elements 0 .. i — np.cumsum on
+        ciphertexts; the left-child sums over the bins of a gradient histogram, encrypted CDFs, running balances.  With
+        block=B the vector is len(self) / B consecutive sequences of B rows, each scanned on its own:
+        x.reshape(-1, B).cumsum(axis=1).ravel(), the form in which segment_sum(bins, S) hands back F histograms (block=S).
+        len(self) % B != 0 or B < 1 raises ValueError, a block that is not an integer TypeError; block=1 returns the aligned rows.
+        The vector is aligned to its smallest exponent first, as sum() does, and every output row carries that exponent.
+        Row i is the canonical residue prod_{j <= i} c_j mod n^2 over the aligned rows of its sequence: bit for bit what
+        `self.decrease_exponent_to(min)[:i+1].sum()` and the reference's chain of `+` (EncryptedNumber._raw_add,
+        phe/paillier.py:705-719) return.
+        One limb group walks the rows of a task and stores the running product after every row; the tasks' totals are
+        reduced, scanned in turn and handed back as carries (Engine.scan_launch_dev): about two pair products per element.  A
+        resident vector gives a resident result (in the pair form if the vector is in it); a host vector goes up, through the
+        same kernel, and back.  Without that kernel (no split-modulus engine for the key width) the sums are formed by log-step
+        doubling with the element-wise product — round d = 1, 2, 4, ... multiplies row i by row i - d wherever
+        (i mod B) >= d: same bits."""
+        pk = self.public_key
+        n = len(self)
+        if block is not None:
+            if isinstance(block, (bool, np.bool_)) or not isinstance(block, (int, np.integer)):
+                raise TypeError("block must be an integer")
+            block = int(block)
+            if block < 1:
+                raise ValueError("block must be at least 1")
+            if n % block:
+                raise ValueError("%d rows are not a whole number of blocks of %d" % (n, block))
+        eng = self._eng()
+        if n == 0:
+            empty = DeviceArray(eng.ctx, 0, eng.ct_limbs) if self.on_device else np.zeros((0, eng.ct_limbs), dtype=np.uint32)
+            return EncryptedVector(pk, empty, np.zeros(0, dtype=np.int64))
+        exp = int(self._exps.min())
+        cur = self.decrease_exponent_to(exp)
+        exps = np.full(n, exp, dtype=np.int64)
+        if eng.has_segment_scan():
+            if self.on_device:
+                store = cur._store if cur._pair else cur._plain_rows()
+                out = eng.segment_scan_dev(store, cur._pair, block, want_pair=self._pair)
+                return EncryptedVector(pk, out, exps, _pair=self._pair)
+            out = eng.segment_scan_dev(eng.upload_cipher(cur._limbs), False, block)
+            return EncryptedVector(pk, out.to_host(), exps)
+        # log-step doubling: after round d row i holds the product of the rows i - 2d + 1 .. i of its sequence
+        limbs = cur._plain_rows() if self.on_device else cur._limbs
+        gather = (lambda a, i: self._gather_dev(eng, a, i)) if self.on_device else (lambda a, i: np.ascontiguousarray(a[i]))
+        mul = eng.raw_add_dev if self.on_device else eng.raw_add
+        within = np.arange(n, dtype=np.int64) % (n if block is None else block)
+        d = 1
+        while d <= int(within.max()):
+            upper = np.nonzero(within >= d)[0]
+            prod = mul(gather(limbs, upper), gather(limbs, upper - d))
+            take = np.arange(n, dtype=np.int64) + len(upper)
+            take[upper] = np.arange(len(upper))
+            if self.on_device:
+                both = DeviceArray(eng.ctx, len(upper) + n, eng.ct_limbs)
+                eng.ctx.d2d(both.ptr, prod.ptr, prod.nbytes)
+                eng.ctx.d2d(both.ptr + prod.nbytes, limbs.ptr, limbs.nbytes)
+                eng.ctx.sync()
+            else:
+                both = np.concatenate([prod, limbs])
+            limbs, d = gather(both, take), 2 * d
+        return EncryptedVector(pk, limbs, exps)
+
     @staticmethod
     def _gather_dev(eng, rows, index):
         idx = DeviceArray.from_host(eng.ctx, np.asarray(index, dtype=np.uint32))
