@@ -17,6 +17,13 @@ sum over the bins — which the feature holder can form on the ciphertexts as we
 
     left = hist.cumsum(block=n_bins)                    # per feature: sum of the gradients left of every threshold
 
+The sums are small next to a plaintext of the key (a 53-bit mantissa at the vector's exponent, plus the bits that adding the
+samples adds), so the feature holder packs several of them into every ciphertext it sends back, and the label holder pays one
+decrypt per packed row instead of one per number:
+
+    packed = left.pack(slots, slot_bits)                # slot j of row b: sum number b * slots + j
+    sums = privkey.decrypt_packed(packed, slots, slot_bits, count=len(left))
+
 python examples/encrypted_histogram_batched.py [key_length] [samples] [features] [bins]
 """
 import os
@@ -55,6 +62,15 @@ def run(key_length=1024, n_samples=2048, n_features=4, n_bins=16, device=None, v
     enc_left = enc_hist.cumsum(block=n_bins)                                    # feature holder: left-child sums of every threshold
     t4 = time.perf_counter()
     left = np.array(privkey.decrypt_batch(enc_left)).reshape(n_features, n_bins)
+    # the feature holder packs the sums before they go back.  The exponent of the rows is public and |gradient| < 1, so a sum of at
+    # most n_samples gradients is below n_samples * BASE^-exponent in magnitude: that many bits, and one for the sign, per slot
+    t5 = time.perf_counter()
+    slot_bits = 1 + int(np.ceil(np.log2(n_samples))) + 4 * -min(enc_left.exponents)
+    slots = (pubkey.max_int.bit_length() - 1) // slot_bits
+    enc_packed = enc_left.pack(slots, slot_bits)
+    t6 = time.perf_counter()
+    unpacked = np.array(privkey.decrypt_packed(enc_packed, slots, slot_bits, count=len(enc_left))).reshape(n_features, n_bins)
+    t7 = time.perf_counter()
 
     clear = np.stack([np.bincount(b[in_node], weights=gradients[in_node], minlength=n_bins) for b in bins])
     err = float(np.max(np.abs(hist - clear)))
@@ -68,6 +84,11 @@ def run(key_length=1024, n_samples=2048, n_features=4, n_bins=16, device=None, v
         print("max |histogram - np.bincount| %.3e" % err)
         print("encrypted left-child sums:    %.3f s  (cumsum over the %d bins of every feature)" % (t4 - t3, n_bins))
         print("max |left sums - np.cumsum|   %.3e" % err_left)
+        print("pack the left-child sums:     %.3f s  (%d ciphertexts of %d slots x %d bits instead of %d)"
+              % (t6 - t5, len(enc_packed), slots, slot_bits, len(enc_left)))
+        print("decrypt the packed sums:      %.3f s  (max |unpacked - decrypted one by one| %.3e)"
+              % (t7 - t6, float(np.max(np.abs(unpacked - left)))))
+    assert np.array_equal(unpacked, left)
     assert err < 1e-9, err
     assert err_left < 1e-9, err_left
     return hist, clear

@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 8
+#define PHE_HIP_ABI_VERSION 9
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -290,6 +290,17 @@ int phe_hip_segment_reduce_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_
 int phe_hip_segment_scan_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows,
                              const uint64_t* task_ptr, const uint32_t* carry_pair, const uint32_t* carry_idx,
                              uint32_t* out_pair, size_t tasks, void* stream);
+/* Ciphertext packing: out_pair[t] (tasks pair rows) = prod_{j < slots} rows[t*slots + j] ^ (2^(slot_bits*j)) mod n^2, an
+ * encryption of x_0 + x_1 2^B + x_2 2^(2B) + ... for the plaintexts x_j of the task's rows (B = slot_bits) — with the reference
+ * the chain c_0*1 + c_1*(1 << B) + ...: every term EncryptedNumber.__mul__ -> _raw_mul (phe/paillier.py:721-751:
+ * powmod(c, 2^(B j), n^2)), joined by __add__ -> _raw_add (:705-719).  Horner's rule from the top slot down,
+ * acc <- acc^(2^B) * c_j with the accumulator in registers (csrc/segment_core.h segment_pack_body): slot_bits squarings and ONE
+ * pair product per input row instead of a B*j-bit exponentiation per row.  rows: as phe_hip_segment_reduce_dev.  Task t owns the
+ * CONSECUTIVE rows t*slots .. t*slots + slots; a row at or beyond n_rows contributes the ciphertext 1.  tasks must be
+ * ceil(n_rows / slots); that, slots == 0 or slot_bits == 0: EINVAL.  The caller sees to it that slots*slot_bits bits fit the
+ * plaintext space.  EINVAL without the split-modulus engine. */
+int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, uint32_t slots,
+                             uint32_t slot_bits, uint32_t* out_pair, size_t tasks, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

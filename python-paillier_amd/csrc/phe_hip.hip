@@ -124,6 +124,7 @@ namespace phe {
 namespace seg {  // kernels_seg.hip
 int launch_segment_reduce(int G, int L, int blocks, hipStream_t st, const SegmentArgs& A);
 int launch_segment_scan(int G, int L, int blocks, hipStream_t st, const ScanArgs& A);
+int launch_segment_pack(int G, int L, int blocks, hipStream_t st, const PackArgs& A);
 }  // namespace seg
 }  // namespace phe
 
@@ -2133,6 +2134,42 @@ int phe_hip_segment_scan_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_ar
     ctx->last_geom_pub = geom_code(sp.G, sp.L);
     const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
     if (phe::seg::launch_segment_scan(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// out_pair[t] = prod_{j < slots} rows[t*slots + j] ^ (2^(slot_bits*j)) (segment_core.h segment_pack_body): `slots` ciphertexts of
+// small plaintexts packed into one — the chain c_0*1 + c_1*(1 << B) + ... of _raw_mul (phe/paillier.py:721-751) and _raw_add
+// (:705-719) — by Horner's rule, slot_bits squarings and one pair product per input row.  The geometry is the pair rung of
+// `tasks` limb groups.
+int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, uint32_t slots,
+                             uint32_t slot_bits, uint32_t* out_pair, size_t tasks, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (slots == 0 || slot_bits == 0) return fail(PHE_HIP_EINVAL, "slots and slot_bits must be at least 1");
+    if (tasks != n_rows / slots + (n_rows % slots ? 1 : 0)) return fail(PHE_HIP_EINVAL, "tasks must be ceil(n_rows / slots)");
+    if (tasks == 0) return PHE_HIP_OK;
+    if (!out_pair || !rows) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (n_rows > 0xFFFFFFFFull || tasks > 0xFFFFFFFFull) return fail(PHE_HIP_EINVAL, "row numbers are 32-bit");
+    if (int rc = bind_device(ctx)) return rc;
+    if (!(ctx->use_split && ctx->d_nsplit.G)) return fail(PHE_HIP_EINVAL, "the pair form needs the split-modulus engine");
+    PHE_CTX_ORDER(ctx, stream);
+    const DevSplit& sp = pick_pair_split(ctx, tasks);
+    PackArgs A;
+    A.mod = sp.c;
+    A.rows = rows;
+    A.rows_are_pair = rows_are_pair ? 1 : 0;
+    A.limbs = ctx->pub.s2;
+    A.chunks = chunks_for(ctx->pub.s2, sp.rows);
+    A.n_rows = n_rows;
+    A.slots = slots;
+    A.slot_bits = slot_bits;
+    A.out = out_pair;
+    A.tasks = tasks;
+    ctx->last_path = 0;
+    ctx->last_geom_pub = geom_code(sp.G, sp.L);
+    const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
+    if (phe::seg::launch_segment_pack(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
         return fail(PHE_HIP_EINVAL, "unsupported split geometry");
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;

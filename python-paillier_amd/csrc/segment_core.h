@@ -157,4 +157,78 @@ PHE_DEV void segment_scan_body(const ScanArgs& A, uint32_t* lds_row, uint32_t sl
     }
 }
 
+// ---- packing: out[t] = prod_{j < slots} rows[t*slots + j] ^ (2^(slot_bits*j)) — many small plaintexts in one ciphertext ------
+// E(x_0) * E(x_1)^(2^B) * E(x_2)^(2^(2B)) * ... encrypts x_0 + x_1 2^B + x_2 2^(2B) + ... (EncryptedVector.pack): with the
+// reference the chain c_0*1 + c_1*(1 << B) + ..., every term EncryptedNumber.__mul__ -> _raw_mul (phe/paillier.py:721-751,
+// powmod(c, 2^(B j), n^2)), joined by __add__ -> _raw_add (:705-719).  Horner's rule from the top slot down,
+// acc <- acc^(2^B) * c_j, shares the squarings between the slots: B squarings and one product per input row, the accumulator
+// in registers as in the two walks above.  Task t owns the CONSECUTIVE rows t*slots .. t*slots + slots; a row at or past
+// n_rows (the ragged last task) contributes the ciphertext 1.
+// Lock step: the trip counts slots and slot_bits are kernel arguments, the same in every group of every wavefront, so the loops
+// need no ballot; a slot past the last task and a row past the end still execute every squaring and product of the wave — the
+// product by the pair of 1 (mod.e), read from a valid address (row 0 where the wave converts residues) — and a slot past the
+// last task stores nothing.
+struct PackArgs {
+    SplitConsts mod;
+    const uint32_t* rows;  // rows_are_pair: (n_rows, 2H) pair rows; else (n_rows, limbs) canonical residues in 32-bit words
+    int rows_are_pair;     // (the launcher picks segment_pack_body<G, L, PAIR> by it)
+    int limbs;             // 32-bit words of a residue row
+    int chunks;            // ceil(32*limbs / (29 rows))
+    uint64_t n_rows;       // > 0; a row number at or above it is not read
+    uint32_t slots;        // > 0: input rows per output row
+    uint32_t slot_bits;    // > 0: squarings between two slots
+    uint32_t* out;         // (tasks, 2H) pair rows
+    uint64_t tasks;        // > 0, = ceil(n_rows / slots), at most 2^32
+};
+
+template <int G, int L, bool PAIR>
+PHE_DEV void segment_pack_body(const PackArgs& A, uint32_t* lds_row, uint32_t slot, uint32_t total_slots, uint32_t lane) {
+    constexpr int H = G * L, S2 = 2 * H;
+    const Lanes<G> ln(lane);
+    const uint32_t g = ln.g;
+    SplitLane<G, L> K;
+    load_row<L>(K.n, A.mod.n, g);
+    K.n0inv = A.mod.n0inv;
+    K.rows_ = A.mod.rows;
+    K.row_a = lds_row;
+    K.row_c = lds_row + H;
+    const uint64_t n_iter = (A.tasks + total_slots - 1) / total_slots;
+    for (uint64_t it = 0; it < n_iter; ++it) {
+        // (every per-lane index in ONE register across the squarings: tasks <= 2^32, and `base`, `left` are wave-uniform)
+        const uint64_t base = it * (uint64_t)total_slots, left = A.tasks - base;
+        const bool live = left > 0xFFFFFFFFull || slot < (uint32_t)left;
+        const uint32_t t = live ? (uint32_t)base + slot : 0u;  // (task 0 is always there)
+        uint32_t X0[L], X1[L], Y0[L], Y1[L];
+        load_row<L>(X0, wave::reread_ptr(A.mod.e), g);
+        load_row<L>(X1, wave::reread_ptr(A.mod.e) + H, g);
+        for (uint32_t el = A.slots; el-- > 0;) {  // from the top slot down
+            if (el + 1 != A.slots)
+                for (uint32_t s = 0; s < A.slot_bits; ++s) split_square<G, L>(X0, X1, K, ln);
+            uint64_t r = (uint64_t)t * A.slots + el;
+            const bool mine = live && r < A.n_rows;
+            if (!mine) r = 0;
+            if constexpr (PAIR) {
+                // (the row's address and the lane position are re-read here: left to itself the compiler loads the row before
+                //  the squarings, keeps it alive across them and spills other values for it)
+                const uint32_t* src = wave::reread_vptr(mine ? A.rows + r * (uint64_t)S2 : A.mod.e);
+                const uint32_t gi = wave::reread(g);
+                load_row<L>(Y0, src, gi);
+                load_row<L>(Y1, src + H, gi);
+            } else {
+                split_conv<G, L>(Y0, Y1, A.rows + r * (uint64_t)A.limbs, A.limbs, A.chunks, A.mod, K, ln);
+                if (!mine) {
+                    load_row<L>(Y0, wave::reread_ptr(A.mod.e), g);
+                    load_row<L>(Y1, wave::reread_ptr(A.mod.e) + H, g);
+                }
+            }
+            split_mul<G, L>(X0, X1, Y0, Y1, K, ln);
+        }
+        if (live) {
+            uint32_t* dst = A.out + (uint64_t)wave::reread(t) * S2;
+            store_row<L>(dst, X0, g);
+            store_row<L>(dst + H, X1, g);
+        }
+    }
+}
+
 }  // namespace phe

@@ -927,6 +927,29 @@ class Engine:
             return carry
         return self.from_pair_dev(carry)                     # (synchronises)
 
+    # ---- ciphertext packing on resident rows (include/phe_hip.h phe_hip_segment_pack_dev) ------------------------------------
+    def has_segment_pack(self):
+        """True when packing has its kernel: the pair form is offered and the backend has the entry point"""
+        return bool(self.pair_form()) and hasattr(self.ctx, "segment_pack_dev")
+
+    def segment_pack_dev(self, store, is_pair, slots, slot_bits, want_pair=False):
+        """out[t] = prod_{j < slots} store[t * slots + j] ^ (2^(slot_bits * j)) over ceil(rows / slots) output rows, rows past
+        the end counting as 1: the chain c_0*1 + c_1*(1 << B) + ... of _raw_mul (phe/paillier.py:721-751) and _raw_add
+        (:705-719) by Horner's rule, one launch, nothing planned on the host.  store: resident rows, pair form (is_pair) or
+        canonical residues; returns a DeviceArray of canonical residues, or of pair rows (want_pair)."""
+        words = self.pair_form()
+        if store.rows == 0:
+            return DeviceArray(self.ctx, 0, words if want_pair else self.ct_limbs)
+        if store.cols != (words if is_pair else self.ct_limbs):
+            raise ValueError("the store has rows of %d words" % store.cols)
+        tasks = -(-store.rows // int(slots))
+        out = DeviceArray(self.ctx, tasks, words)
+        self.ctx.segment_pack_dev(store.ptr, is_pair, store.rows, int(slots), int(slot_bits), out.ptr, tasks)
+        if want_pair:
+            self.ctx.sync()
+            return out
+        return self.from_pair_dev(out)                       # (synchronises)
+
     def obfuscate_fresh_dev(self, c, rows=None):
         """obfuscate_dev with freshly drawn obfuscators, chunked like raw_encrypt_fresh (draw and upload of the next
         chunk under the kernels of the current one).  rows: indices that get a fresh r (None = all); the others get

@@ -18,7 +18,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("PHE_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libphe_hip.so")
 
 OK, EINVAL, EHIP, ENOINVERSE = 0, 1, 2, 3
-ABI_VERSION = 8          # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
+ABI_VERSION = 9          # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
 
 _lib = None
 
@@ -114,6 +114,7 @@ def lib():
         L.phe_hip_pair_reduce_dev.argtypes = [vp, vp, sz, vp, vp]
         L.phe_hip_segment_reduce_dev.argtypes = [vp, vp, ci, sz, vp, vp, vp, vp, sz, vp]
         L.phe_hip_segment_scan_dev.argtypes = [vp, vp, ci, sz, vp, vp, vp, vp, sz, vp]
+        L.phe_hip_segment_pack_dev.argtypes = [vp, vp, ci, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
         L.phe_hip_pair_powmod_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp]
         L.phe_hip_pair_multiexp_rows_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, sz, vp]
         _lib = L
@@ -136,7 +137,7 @@ EXPORTED_SYMBOLS = [
     "phe_hip_ctx_ladder", "phe_hip_ctx_set_group", "phe_hip_ctx_load_ladder", "phe_hip_ctx_last_launch", "phe_hip_ctx_release_scratch",
     "phe_hip_pair_words", "phe_hip_to_pair_dev", "phe_hip_pair_mul_dev", "phe_hip_from_pair_dev", "phe_hip_pair_reduce_dev",
     "phe_hip_pair_powmod_dev", "phe_hip_pair_multiexp_rows_dev", "phe_hip_segment_reduce_dev",
-    "phe_hip_segment_scan_dev",
+    "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev",
 ]
 
 
@@ -378,6 +379,11 @@ class Context:
         phe_hip_segment_scan_dev)"""
         _check(lib().phe_hip_segment_scan_dev(self._h, rows_ptr, 1 if rows_are_pair else 0, n_rows, task_ptr, carry_ptr, carry_idx_ptr,
                                               out_ptr, tasks, stream))
+
+    def segment_pack_dev(self, rows_ptr, rows_are_pair, n_rows, slots, slot_bits, out_ptr, tasks, stream=0):
+        """out[t] (pair rows) = prod_j rows[t*slots + j] ^ (2^(slot_bits*j)) (include/phe_hip.h phe_hip_segment_pack_dev)"""
+        _check(lib().phe_hip_segment_pack_dev(self._h, rows_ptr, 1 if rows_are_pair else 0, n_rows, slots, slot_bits, out_ptr, tasks,
+                                              stream))
 
     # ---- host-array entry points (numpy uint32, row-major (batch, limbs)) ----
     def encrypt(self, m, r):

@@ -733,6 +733,66 @@ class EncryptedVector(object):
             limbs, d = gather(both, take), 2 * d
         return EncryptedVector(pk, limbs, exps)
 
+    def pack(self, slots, slot_bits):
+        """Ciphertext packing -> EncryptedVector of ceil(len(self) / slots) rows: row b is an encryption of
+        x[b*S] + x[b*S + 1] * 2^B + x[b*S + 2] * 2^(2B) + ... (S = slots, B = slot_bits) — S small plaintexts travel, and are
+        decrypted (PaillierPrivateKey.decrypt_packed), as ONE ciphertext; packed vectors still add slot by slot.  What a party
+        does with the histograms of segment_sum / cumsum before it ships them to the key holder (SecureBoost+ "ciphertext
+        compression").
+        The vector is aligned to its smallest exponent first, as sum() does, and every output row carries that exponent.
+        Row b is the canonical residue prod_j c[b*S + j] ^ (2^(B*j)) mod n^2 over the aligned rows, rows past the end of the
+        vector counting as the ciphertext 1: bit for bit the reference's chain c[bS]*1 + c[bS+1]*(1 << B) + ...
+        (EncryptedNumber.__mul__ -> _raw_mul, phe/paillier.py:721-751, then __add__ -> _raw_add, :705-719).
+        slots or slot_bits that is not an integer raises TypeError, one below 1 ValueError, and so does
+        slots * slot_bits > public_key.max_int.bit_length() - 1: under that bound every factor 2^(B*j) is a plaintext the
+        reference's encode accepts, and a packed value whose slots all lie in [-2^(B-1), 2^(B-1)) stays inside +-max_int.
+        WHAT CANNOT BE CHECKED UNDER ENCRYPTION: a slot whose true value (mantissa at the common exponent, after every later
+        addition of packed vectors) leaves [-2^(B-1), 2^(B-1)) spills into its neighbour, silently.  Choosing slot_bits with
+        enough headroom is the caller's job.
+        One limb group forms an output row by Horner's rule from the top slot down, acc <- acc^(2^B) * c_j, with the accumulator
+        in registers (Engine.segment_pack_dev): B squarings and one pair product per element.  A resident vector gives a
+        resident result (in the pair form if the vector is in it); a host vector goes up, through the same kernel, and back.
+        Without that kernel (no split-modulus engine for the key width) every row is raised to its own power 2^(B*j) by
+        _raw_mul and the powers are summed by segment_sum with the ids i // S: same bits."""
+        pk = self.public_key
+        for name, value in (("slots", slots), ("slot_bits", slot_bits)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+                raise TypeError("%s must be an integer" % name)
+            if value < 1:
+                raise ValueError("%s must be at least 1" % name)
+        slots, slot_bits = int(slots), int(slot_bits)
+        bound = pk.max_int.bit_length() - 1
+        if slots * slot_bits > bound:
+            raise ValueError("slots * slot_bits = %d bits do not fit the %d bits a plaintext of this key holds"
+                             % (slots * slot_bits, bound))
+        n = len(self)
+        eng = self._eng()
+        if n == 0:
+            empty = DeviceArray(eng.ctx, 0, eng.ct_limbs) if self.on_device else np.zeros((0, eng.ct_limbs), dtype=np.uint32)
+            return EncryptedVector(pk, empty, np.zeros(0, dtype=np.int64))
+        exp = int(self._exps.min())
+        cur = self.decrease_exponent_to(exp)
+        if slots == 1:
+            return cur
+        n_out = -(-n // slots)
+        exps = np.full(n_out, exp, dtype=np.int64)
+        if eng.has_segment_pack():
+            if self.on_device:
+                store = cur._store if cur._pair else cur._plain_rows()
+                out = eng.segment_pack_dev(store, cur._pair, slots, slot_bits, want_pair=self._pair)
+                return EncryptedVector(pk, out, exps, _pair=self._pair)
+            out = eng.segment_pack_dev(eng.upload_cipher(cur._limbs), False, slots, slot_bits)
+            return EncryptedVector(pk, out.to_host(), exps)
+        # every row to its own power (integers: exponent 0, below n - max_int: the direct branch of _raw_mul), then the sums
+        index = np.arange(n, dtype=np.int64)
+        powers = [1 << (slot_bits * j) for j in (index % slots).tolist()]
+        if self.on_device:
+            limbs = eng.raw_mul_dev(cur._plain_rows(), powers)
+        else:
+            limbs = eng.raw_mul(cur._limbs, powers)
+        out = EncryptedVector(pk, limbs, np.full(n, exp, dtype=np.int64)).segment_sum(index // slots, n_out)
+        return out.to_pair() if self._pair else out
+
     @staticmethod
     def _gather_dev(eng, rows, index):
         idx = DeviceArray.from_host(eng.ctx, np.asarray(index, dtype=np.uint32))

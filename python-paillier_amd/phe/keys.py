@@ -473,6 +473,121 @@ class PaillierPrivateKey(object):
             return EncodedNumber.decode_limbs(self.public_key, plain, vector.exponent_array)
         return Encoding.decode_many(self.public_key, eng.to_ints(plain), vector.exponents)
 
+    def _raw_plain_chunks(self, vector):
+        """(lo, hi, plaintext limb rows on the host) over an EncryptedVector, by the raw decrypt paths of decrypt_batch:
+        resident or host, in chunks whose download overlaps the kernels of the next"""
+        eng = self._get_engine()
+        fl = self._get_fleet()
+        if vector.on_device and fl is not None:
+            eng = self.public_key._engine_for(vector._store)
+        limbs = vector.limbs(be_secure=False)
+        if not vector.on_device and fl is not None and len(fl.shards(len(vector))) > 1:
+            lo = 0
+            for plain in fl.run(len(vector), lambda e, lo, hi: e.raw_decrypt(limbs[lo:hi])):   # (contiguous shards, in order)
+                yield lo, lo + len(plain), plain
+                lo += len(plain)
+        elif vector.on_device or hasattr(eng.ctx, "decrypt_dev"):
+            chunks = eng.raw_decrypt_dev_chunks(limbs) if vector.on_device else eng.raw_decrypt_host_chunks(limbs)
+            for lo, hi, plain in chunks:
+                yield lo, hi, plain
+        elif len(vector):
+            yield 0, len(vector), eng.raw_decrypt(limbs)
+
+    def decrypt_packed(self, vector, slots, slot_bits, count=None, Encoding=None):
+        """The values of a vector packed by EncryptedVector.pack(slots, slot_bits) (and of sums of such vectors) -> list of
+        decoded ints / floats, like decrypt_batch: ONE decrypt per `slots` values.  Value number b * slots + j is slot j of
+        row b.  The rows are decrypted through the raw decrypt paths of decrypt_batch; each plaintext m is unpacked on the host:
+        v = m if m <= max_int, m - n if m >= n - max_int (in between: OverflowError, as EncodedNumber.decode); slot by slot
+        d_j = ((v + 2^(B-1)) mod 2^B) - 2^(B-1), v <- (v - d_j) >> B; what is left of v after the last slot must be 0
+        (OverflowError: the packed value did not fit slots * slot_bits bits).  d_j is decoded as
+        Encoding(public_key, d_j % n, exponent of row b).decode().  count keeps the first `count` values (default
+        len(vector) * slots; outside [0, len(vector) * slots]: ValueError).
+        A slot that left [-2^(B-1), 2^(B-1)) before it was decrypted has spilled into its neighbour and cannot be told from a
+        legitimate value: see EncryptedVector.pack."""
+        from .ciphertext import EncryptedVector
+        for name, value in (("slots", slots), ("slot_bits", slot_bits)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+                raise TypeError("%s must be an integer" % name)
+            if value < 1:
+                raise ValueError("%s must be at least 1" % name)
+        slots, slot_bits = int(slots), int(slot_bits)
+        if not isinstance(vector, EncryptedVector):
+            vector = EncryptedVector.from_numbers(self.public_key, vector)
+        if self.public_key != vector.public_key:
+            raise ValueError('encrypted_number was encrypted against a different key!')
+        total = len(vector) * slots
+        if count is None:
+            count = total
+        if isinstance(count, (bool, np.bool_)) or not isinstance(count, (int, np.integer)):
+            raise TypeError("count must be an integer")
+        count = int(count)
+        if not 0 <= count <= total:
+            raise ValueError("count must lie in [0, %d]" % total)
+        plain_decode = Encoding is None or Encoding is EncodedNumber
+        out, exps = [], vector.exponent_array
+        for lo, hi, plain in self._raw_plain_chunks(vector):
+            out += self._unpack_plain(plain, exps[lo:hi], slots, slot_bits, None if plain_decode else Encoding)
+        del out[count:]
+        return out
+
+    def _unpack_plain(self, plain, exps, slots, slot_bits, Encoding):
+        """the decoded slots of the plaintext rows `plain` (host limbs), row after row (decrypt_packed).  With
+        u = v + sum_j 2^(B-1) 2^(B j) the slots are the B-bit digits of u less 2^(B-1), and v fits slots * B bits exactly when
+        0 <= u < 2^(slots * B): one Python integer per ROW; for B <= 64 the digits are cut out of the rows' 64-bit words by
+        numpy, `slots` vector operations whatever the number of rows."""
+        from . import _native
+        pk = self.public_key
+        n, max_int = pk.n, pk.max_int
+        S, B = slots, slot_bits
+        half = 1 << (B - 1)
+        offset = half * (((1 << (S * B)) - 1) // ((1 << B) - 1))     # 2^(B-1) in every slot
+        us = []
+        for m in _native.limbs_to_ints(plain):
+            if m <= max_int:
+                v = m
+            elif m >= n - max_int:
+                v = m - n
+            else:
+                raise OverflowError('Overflow detected in decrypted number')
+            u = v + offset
+            if u < 0 or u >> (S * B):
+                raise OverflowError('a packed value does not fit %d slots of %d bits' % (S, B))
+            us.append(u)
+        rows = len(us)
+        row_exps = np.repeat(np.asarray(exps, dtype=np.int64), S)
+        if rows == 0:
+            return []
+        log2b = int(round(EncodedNumber.LOG2_BASE))
+        one_kind = bool((row_exps == 0).all() or (row_exps < 0).all())
+        if (Encoding is None and B <= 64 and (1 << log2b) == EncodedNumber.BASE and one_kind
+                and int(row_exps.min()) * log2b >= -960):
+            n_words = (S * B + 63) // 64 + 1                         # (one spare word: a digit may straddle the last one)
+            words = np.frombuffer(b"".join(u.to_bytes(8 * n_words, "little") for u in us), dtype=np.uint64).reshape(rows, n_words)
+            digits = np.empty((rows, S), dtype=np.uint64)
+            mask = np.uint64((1 << B) - 1)
+            for j in range(S):
+                w, off = divmod(B * j, 64)
+                d = words[:, w] >> np.uint64(off)
+                if off + B > 64:
+                    d = d | (words[:, w + 1] << np.uint64(64 - off))
+                digits[:, j] = d & mask
+            if B == 64:
+                vals = (digits ^ np.uint64(half)).view(np.int64)     # digit - 2^63 in two's complement
+            else:
+                vals = digits.view(np.int64) - np.int64(half)
+            vals = vals.reshape(-1)
+            if row_exps[0] < 0:
+                # correctly rounded int64 -> float64, then an exact power-of-two scaling = the reference's true division
+                return np.ldexp(vals.astype(np.float64), row_exps * log2b).tolist()
+            return vals.tolist()
+        mask = (1 << B) - 1
+        cls = EncodedNumber if Encoding is None else Encoding
+        out = []
+        for u, e in zip(us, np.asarray(exps, dtype=np.int64).tolist()):
+            for j in range(S):
+                out.append(cls(pk, (((u >> (B * j)) & mask) - half) % n, e).decode())
+        return out
+
 
 class PaillierPrivateKeyring(Mapping):
     def __init__(self, private_keys=None):
