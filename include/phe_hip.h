@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 9
+#define PHE_HIP_ABI_VERSION 10
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -301,6 +301,20 @@ int phe_hip_segment_scan_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_ar
  * plaintext space.  EINVAL without the split-modulus engine. */
 int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, uint32_t slots,
                              uint32_t slot_bits, uint32_t* out_pair, size_t tasks, void* stream);
+/* The slot codec of packed plaintexts (csrc/slot_codec.h): S = slots signed values of B = slot_bits bits (1 <= B <= 64,
+ * S*B <= max_int.bit_length() - 1) per plaintext row, the conventions of EncryptedVector.pack / decrypt_packed.  Both kernels
+ * move bit fields and are bound by memory.
+ * pack: m_rows[b] (rows x n_limbs words) = (sum_{j < S} values[b*S + j] * 2^(B j)) mod n, every value in [-2^(B-1), 2^(B-1))
+ * (the caller checks that; only the low B bits of value + 2^(B-1) are placed); values at or beyond count read as 0.  rows must
+ * be ceil(count / slots).
+ * unpack: values[b*S + j] (rows*S int64) = slot j of the number that m_rows[b] stands for (m if m <= max_int, m - n if
+ * m >= n - max_int), status[b] = 0, or 1: m lies between the two ranges (the overflow of EncodedNumber.decode,
+ * phe/encoding.py:221), or 2: the number does not fit S*B bits; the values of a row with a non-zero status are unspecified.
+ * slots == 0, slot_bits outside [1, 64], S*B beyond the bound, a wrong `rows`, a null buffer: EINVAL. */
+int phe_hip_slots_pack_dev(phe_hip_ctx* ctx, const int64_t* values, size_t count, uint32_t slots, uint32_t slot_bits,
+                           uint32_t* m_rows, size_t rows, void* stream);
+int phe_hip_slots_unpack_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t rows, uint32_t slots, uint32_t slot_bits,
+                             int64_t* values, uint8_t* status, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

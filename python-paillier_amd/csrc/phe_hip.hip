@@ -31,6 +31,7 @@
 #include "mont_core.h"
 #include "split_core.h"
 #include "segment_core.h"
+#include "slot_codec.h"
 #include "mul_io.h"
 #include "mul_table.h"
 #include "decrypt_tail.h"
@@ -126,6 +127,10 @@ int launch_segment_reduce(int G, int L, int blocks, hipStream_t st, const Segmen
 int launch_segment_scan(int G, int L, int blocks, hipStream_t st, const ScanArgs& A);
 int launch_segment_pack(int G, int L, int blocks, hipStream_t st, const PackArgs& A);
 }  // namespace seg
+namespace slots {  // kernels_slots.hip
+int launch_slots_pack(int G, int K, int blocks, hipStream_t st, const SlotPackArgs& A);
+int launch_slots_unpack(int G, int K, int blocks, hipStream_t st, const SlotUnpackArgs& A);
+}  // namespace slots
 }  // namespace phe
 
 namespace phe {
@@ -420,6 +425,9 @@ struct phe_hip_ctx {
     TailWaveConsts d_tail_wave{};
     int tail_wave_L = 0;
     size_t tail_wave_per_cu = 16;  // batches of up to this many ciphertexts per CU take it (create_private; PHE_HIP_WAVE_TAIL_PER_CU)
+    // the constant rows of the slot codec (slot_codec.h host::slot_const_rows), one device block per (slots, slot_bits) seen
+    struct SlotRows { uint32_t slots, slot_bits; uint32_t* dev; };
+    std::vector<SlotRows> slot_rows;
     // grow-only device scratch
     uint32_t* table = nullptr;
     size_t table_words = 0;
@@ -1473,6 +1481,7 @@ void phe_hip_ctx_destroy(phe_hip_ctx* ctx) {
                         ctx->tmul_blob, ctx->tmul_cols};
     for (const auto& R : ctx->pub_rungs) { bufs.push_back(R.nsq.blob); bufs.push_back(R.nsplit.blob); bufs.push_back(R.nunit.blob); }
     for (const auto& R : ctx->priv_rungs) { bufs.push_back(R.psq.blob); bufs.push_back(R.qsq.blob); bufs.push_back(R.psplit.blob); bufs.push_back(R.qsplit.blob); }
+    for (const auto& R : ctx->slot_rows) bufs.push_back(R.dev);
     for (uint32_t* b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->mapped_host) (void)hipHostFree(ctx->mapped_host);
@@ -2171,6 +2180,99 @@ int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_ar
     const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
     if (phe::seg::launch_segment_pack(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
         return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// ---- the slot codec of packed plaintexts (slot_codec.h, kernels_slots.hip) ----------------------------------------------------
+// the argument checks both entries share; G, K: the geometry of the key's plaintext rows
+static int slots_check(const phe_hip_ctx* ctx, uint32_t slots, uint32_t slot_bits, int& G, int& K) {
+    if (slots == 0 || slot_bits == 0) return fail(PHE_HIP_EINVAL, "slots and slot_bits must be at least 1");
+    if (slot_bits > 64) return fail(PHE_HIP_EINVAL, "the slot codec takes slot_bits up to 64");
+    const int cap = host::slot_capacity_bits(ctx->pub.n.data(), ctx->pub.s1);
+    if ((uint64_t)slots * slot_bits > (uint64_t)cap)
+        return fail(PHE_HIP_EINVAL, "slots * slot_bits exceeds the " + std::to_string(cap) + " bits below max_int");
+    if (!host::slot_geometry(ctx->pub.s1, G, K)) return fail(PHE_HIP_EINVAL, "no slot codec kernel for this key width");
+    return PHE_HIP_OK;
+}
+// the device rows of SlotConsts for (slots, slot_bits): made on first use and kept with the context
+static int slots_consts(phe_hip_ctx* ctx, uint32_t slots, uint32_t slot_bits, int width, SlotConsts& k) {
+    uint32_t* dev = nullptr;
+    for (const auto& R : ctx->slot_rows)
+        if (R.slots == slots && R.slot_bits == slot_bits) dev = R.dev;
+    if (!dev) {
+        if (ctx->slot_rows.size() >= 64) {  // a caller that sweeps shapes: start over (nothing may still read the old rows)
+            HIP_TRY(hipDeviceSynchronize());
+            for (const auto& R : ctx->slot_rows) (void)hipFree(R.dev);
+            ctx->slot_rows.clear();
+        }
+        const std::vector<uint32_t> rows = host::slot_const_rows(ctx->pub.n.data(), ctx->pub.s1, slots, slot_bits, width);
+        HIP_TRY(hipMalloc((void**)&dev, rows.size() * 4));
+        hipError_t e = hipMemcpy(dev, rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            return fail(PHE_HIP_EHIP, std::string("upload of the slot constants: ") + hipGetErrorString(e));
+        }
+        ctx->slot_rows.push_back({slots, slot_bits, dev});
+    }
+    const size_t W = (size_t)width;
+    k.offset = dev;
+    k.n = dev + W;
+    k.max_int = dev + 2 * W;
+    k.neg_low = dev + 3 * W;
+    k.offset_neg = dev + 4 * W;
+    return PHE_HIP_OK;
+}
+
+// m_rows[b] = (sum_j values[b*slots + j] * 2^(slot_bits*j)) mod n (slot_codec.h slots_pack_body): the packed plaintext of
+// `slots` signed values per row, values at or beyond count read as 0
+int phe_hip_slots_pack_dev(phe_hip_ctx* ctx, const int64_t* values, size_t count, uint32_t slots, uint32_t slot_bits,
+                           uint32_t* m_rows, size_t rows, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    int G = 0, K = 0;
+    if (int rc = slots_check(ctx, slots, slot_bits, G, K)) return rc;
+    if (rows != count / slots + (count % slots ? 1 : 0)) return fail(PHE_HIP_EINVAL, "rows must be ceil(count / slots)");
+    if (rows == 0) return PHE_HIP_OK;
+    if (!values || !m_rows) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    SlotPackArgs A;
+    if (int rc = slots_consts(ctx, slots, slot_bits, G * K, A.k)) return rc;
+    A.values = values;
+    A.count = count;
+    A.slots = slots;
+    A.slot_bits = slot_bits;
+    A.m_rows = m_rows;
+    A.rows = rows;
+    A.n_limbs = ctx->pub.s1;
+    if (phe::slots::launch_slots_pack(G, K, grid_blocks(ctx, rows, G, 8), (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "no slot codec kernel for this key width");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// values[b*slots + j] = slot j of the plaintext row m_rows[b], status[b] = 0 / 1 (m in the overflow gap) / 2 (the packed value
+// does not fit slots*slot_bits bits) (slot_codec.h slots_unpack_body)
+int phe_hip_slots_unpack_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t rows, uint32_t slots, uint32_t slot_bits,
+                             int64_t* values, uint8_t* status, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    int G = 0, K = 0;
+    if (int rc = slots_check(ctx, slots, slot_bits, G, K)) return rc;
+    if (rows == 0) return PHE_HIP_OK;
+    if (!m_rows || !values || !status) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    SlotUnpackArgs A;
+    if (int rc = slots_consts(ctx, slots, slot_bits, G * K, A.k)) return rc;
+    A.m_rows = m_rows;
+    A.rows = rows;
+    A.slots = slots;
+    A.slot_bits = slot_bits;
+    A.values = values;
+    A.status = status;
+    A.n_limbs = ctx->pub.s1;
+    if (phe::slots::launch_slots_unpack(G, K, grid_blocks(ctx, rows, G, 8), (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "no slot codec kernel for this key width");
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;
 }

@@ -652,8 +652,12 @@ class Engine:
         return DeviceArray.from_host(self.ctx, self._as_cipher(ints_or_limbs))
 
     def raw_encrypt_dev(self, m, r):
-        m = self.upload_plain([v % self.n for v in m] if not isinstance(m, np.ndarray) else m)
+        """m: Python ints, limb rows, or RESIDENT plaintext rows (a DeviceArray, e.g. of slots_pack_dev: they stay in HBM)"""
+        if not isinstance(m, DeviceArray):
+            m = self.upload_plain([v % self.n for v in m] if not isinstance(m, np.ndarray) else m)
         r = self.upload_plain(r)
+        if r.rows != m.rows:
+            raise ValueError("%d obfuscators for %d plaintexts" % (r.rows, m.rows))
         out = DeviceArray(self.ctx, m.rows, self.ct_limbs)
         self._encrypt_dev(m.ptr, r.ptr, out.ptr, m.rows)
         self.ctx.sync()
@@ -671,8 +675,10 @@ class Engine:
         """raw_encrypt with freshly drawn obfuscators, in chunks: the draw (the kernel CSPRNG, host side) and the upload
         of chunk k+1 overlap the kernel of chunk k — the kernels are queued on a non-blocking stream, so the blocking
         copies (NULL stream) do not wait for them; the first chunk is half size to shorten the exposed prologue.
-        m: (count, n_limbs) plaintext limbs.  Returns a DeviceArray or a host array."""
-        count = m.shape[0]
+        m: (count, n_limbs) plaintext limbs, on the host or RESIDENT (a DeviceArray: its rows are read where they are).
+        Returns a DeviceArray or a host array."""
+        resident = isinstance(m, DeviceArray)
+        count = m.rows if resident else m.shape[0]
         st = self._launch_stream()
         out = DeviceArray(self.ctx, count, self.ct_limbs)
         host = None if device else np.empty((count, self.ct_limbs), dtype=np.uint32)
@@ -681,7 +687,7 @@ class Engine:
         while lo < count:
             hi = min(count, lo + chunk)
             r = random_lt_n_limbs(self.n, hi - lo, self.n_limbs, out=self.scratch("r", hi - lo, self.n_limbs))
-            m_d = DeviceArray.from_host(self.ctx, m[lo:hi])
+            m_d = m.rows_view(lo, hi) if resident else DeviceArray.from_host(self.ctx, m[lo:hi])
             r_d = DeviceArray.from_host(self.ctx, r)      # synchronous copy: the scratch buffer is free again
             keep += [m_d, r_d]
             if host is not None and st:
@@ -762,8 +768,8 @@ class Engine:
 
     def encrypt_from_obfuscators(self, plaintexts):
         """raw_encrypt(m_i, r_i) for pooled r_i (each used once): (1 + n*m_i) * r_i^n mod n^2 as a DeviceArray, or None
-        if the pool is short.  plaintexts: (count, n_limbs) limb rows or Python ints."""
-        if not isinstance(plaintexts, np.ndarray):
+        if the pool is short.  plaintexts: (count, n_limbs) limb rows, Python ints, or resident rows (a DeviceArray)."""
+        if not isinstance(plaintexts, (np.ndarray, DeviceArray)):
             plaintexts = self.plain_limbs([v % self.n for v in plaintexts])
         rows = self.take_pool_rows(plaintexts.shape[0])
         if rows is None:
@@ -949,6 +955,92 @@ class Engine:
             self.ctx.sync()
             return out
         return self.from_pair_dev(out)                       # (synchronises)
+
+    # ---- the slot codec of packed plaintexts (include/phe_hip.h phe_hip_slots_pack_dev / phe_hip_slots_unpack_dev) ---------------
+    def has_slot_codec(self):
+        """True when the backend has both entries of the slot codec (slot_bits up to 64)"""
+        return hasattr(self.ctx, "slots_pack_dev") and hasattr(self.ctx, "slots_unpack_dev")
+
+    def slots_pack_dev(self, values, slots, slot_bits):
+        """int64 values -> RESIDENT plaintext rows: row b = (sum_j values[b * slots + j] * 2^(slot_bits * j)) mod n, values past
+        the end counting as 0.  Every value must lie in [-2^(slot_bits - 1), 2^(slot_bits - 1)): the caller checks that."""
+        values = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        slots, slot_bits = int(slots), int(slot_bits)
+        rows = -(-len(values) // slots)
+        out = DeviceArray(self.ctx, rows, self.n_limbs)
+        if rows:
+            v = DeviceArray.from_host(self.ctx, values.view(np.uint32))      # (an int64 is two words)
+            self.ctx.slots_pack_dev(v.ptr, len(values), slots, slot_bits, out.ptr, rows)
+            self.ctx.sync()
+        return out
+
+    def slots_unpack_dev(self, plain, slots, slot_bits):
+        """resident plaintext rows -> (int64 array of rows * slots values, uint8 status per row) on the host.  Status 1: the
+        plaintext lies between max_int and n - max_int, 2: the number does not fit slots * slot_bits bits; the values of such
+        a row mean nothing."""
+        slots, slot_bits = int(slots), int(slot_bits)
+        rows = plain.rows
+        values, status = np.empty(rows * slots, dtype=np.int64), np.empty(rows, dtype=np.uint8)
+        if rows:
+            if plain.cols != self.n_limbs:
+                raise ValueError("the rows have %d words" % plain.cols)
+            v, s = DeviceArray(self.ctx, rows * slots, 2), DeviceArray(self.ctx, (rows + 3) // 4, 1)
+            self.ctx.slots_unpack_dev(plain.ptr, rows, slots, slot_bits, v.ptr, s.ptr)
+            self.ctx.sync()
+            self.ctx.d2h(values, v.ptr)
+            self.ctx.d2h(status, s.ptr)
+        return values, status
+
+    def raw_decrypt_unpack_chunks(self, c, slots, slot_bits, chunk=1 << 16):
+        """raw_decrypt + slot unpacking of packed rows as a generator of (lo, hi, int64 values of rows [lo, hi), status bytes):
+        raw_decrypt_dev_chunks / raw_decrypt_host_chunks with the unpack kernel queued behind each chunk's decrypt on the same
+        stream, so that values and status come down instead of limb rows — the plaintext rows never leave HBM.  c: a resident
+        vector (DeviceArray) or host limb rows, uploaded chunk by chunk under the kernels of the chunk before.  The engine's
+        lock is taken around each step, never across a yield."""
+        slots, slot_bits = int(slots), int(slot_bits)
+        with self._lock:
+            st = self._launch_stream()
+        resident = isinstance(c, DeviceArray)
+        rows = c.rows if resident else c.shape[0]
+        if rows == 0:
+            return
+        bounds = [(lo, min(rows, lo + chunk)) for lo in range(0, rows, chunk)]
+        staged, running = {}, {}
+
+        def stage(k):
+            lo, hi = bounds[k]
+            staged[k] = (c.rows_view(lo, hi) if resident else DeviceArray.from_host(self.ctx, c[lo:hi]),
+                         DeviceArray(self.ctx, hi - lo, self.n_limbs), DeviceArray(self.ctx, (hi - lo) * slots, 2),
+                         DeviceArray(self.ctx, (hi - lo + 3) // 4, 1))
+
+        def launch(k):
+            lo, hi = bounds[k]
+            src, plain, vals, stat = running[k] = staged.pop(k)
+            self.ctx.decrypt_dev(src.ptr, plain.ptr, hi - lo, st)
+            self.ctx.slots_unpack_dev(plain.ptr, hi - lo, slots, slot_bits, vals.ptr, stat.ptr, st)
+        try:
+            with self._lock:
+                stage(0)
+                launch(0)
+            for k, (lo, hi) in enumerate(bounds):
+                with self._lock:
+                    if k + 1 < len(bounds):
+                        stage(k + 1)                             # upload under the kernels of chunk k
+                    self.ctx.sync(st)                            # chunk k is complete
+                    if k + 1 < len(bounds):
+                        launch(k + 1)
+                    _, _, vals, stat = running.pop(k)
+                    values, status = np.empty((hi - lo) * slots, dtype=np.int64), np.empty(hi - lo, dtype=np.uint8)
+                    self.ctx.d2h(values, vals.ptr)               # blocking copies on the NULL stream, under chunk k+1
+                    self.ctx.d2h(status, stat.ptr)
+                    del vals, stat
+                yield lo, hi, values, status
+        finally:
+            # a consumer that stops early (an overflow row) drops the generator with the next chunk's kernels still writing:
+            # wait for them before the blocks return to the size-keyed pool
+            self.ctx.sync(st)
+            running.clear()
+            staged.clear()
 
     def obfuscate_fresh_dev(self, c, rows=None):
         """obfuscate_dev with freshly drawn obfuscators, chunked like raw_encrypt_fresh (draw and upload of the next
@@ -1154,7 +1246,10 @@ class Engine:
         return root
 
     def add_plain_dev(self, c, plaintexts):
-        m = self.upload_plain([v % self.n for v in plaintexts] if not isinstance(plaintexts, np.ndarray) else plaintexts)
+        if isinstance(plaintexts, DeviceArray):
+            m = plaintexts
+        else:
+            m = self.upload_plain([v % self.n for v in plaintexts] if not isinstance(plaintexts, np.ndarray) else plaintexts)
         out = DeviceArray(self.ctx, c.rows, self.ct_limbs)
         self.ctx.add_plain_dev(c.ptr, m.ptr, out.ptr, c.rows)
         self.ctx.sync()

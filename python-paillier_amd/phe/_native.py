@@ -18,7 +18,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("PHE_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libphe_hip.so")
 
 OK, EINVAL, EHIP, ENOINVERSE = 0, 1, 2, 3
-ABI_VERSION = 9          # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
+ABI_VERSION = 10         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
 
 _lib = None
 
@@ -115,6 +115,8 @@ def lib():
         L.phe_hip_segment_reduce_dev.argtypes = [vp, vp, ci, sz, vp, vp, vp, vp, sz, vp]
         L.phe_hip_segment_scan_dev.argtypes = [vp, vp, ci, sz, vp, vp, vp, vp, sz, vp]
         L.phe_hip_segment_pack_dev.argtypes = [vp, vp, ci, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
+        L.phe_hip_slots_pack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
+        L.phe_hip_slots_unpack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
         L.phe_hip_pair_powmod_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp]
         L.phe_hip_pair_multiexp_rows_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, sz, vp]
         _lib = L
@@ -137,7 +139,7 @@ EXPORTED_SYMBOLS = [
     "phe_hip_ctx_ladder", "phe_hip_ctx_set_group", "phe_hip_ctx_load_ladder", "phe_hip_ctx_last_launch", "phe_hip_ctx_release_scratch",
     "phe_hip_pair_words", "phe_hip_to_pair_dev", "phe_hip_pair_mul_dev", "phe_hip_from_pair_dev", "phe_hip_pair_reduce_dev",
     "phe_hip_pair_powmod_dev", "phe_hip_pair_multiexp_rows_dev", "phe_hip_segment_reduce_dev",
-    "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev",
+    "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev", "phe_hip_slots_pack_dev", "phe_hip_slots_unpack_dev",
 ]
 
 
@@ -384,6 +386,14 @@ class Context:
         """out[t] (pair rows) = prod_j rows[t*slots + j] ^ (2^(slot_bits*j)) (include/phe_hip.h phe_hip_segment_pack_dev)"""
         _check(lib().phe_hip_segment_pack_dev(self._h, rows_ptr, 1 if rows_are_pair else 0, n_rows, slots, slot_bits, out_ptr, tasks,
                                               stream))
+
+    def slots_pack_dev(self, values_ptr, count, slots, slot_bits, m_ptr, rows, stream=0):
+        """m_rows[b] = (sum_j values[b*slots + j] * 2^(slot_bits*j)) mod n (include/phe_hip.h phe_hip_slots_pack_dev)"""
+        _check(lib().phe_hip_slots_pack_dev(self._h, values_ptr, count, slots, slot_bits, m_ptr, rows, stream))
+
+    def slots_unpack_dev(self, m_ptr, rows, slots, slot_bits, values_ptr, status_ptr, stream=0):
+        """int64 slots and one status byte per plaintext row (include/phe_hip.h phe_hip_slots_unpack_dev)"""
+        _check(lib().phe_hip_slots_unpack_dev(self._h, m_ptr, rows, slots, slot_bits, values_ptr, status_ptr, stream))
 
     # ---- host-array entry points (numpy uint32, row-major (batch, limbs)) ----
     def encrypt(self, m, r):

@@ -25,6 +25,9 @@ DEFAULT_KEYSIZE = 3072
 # scalar encrypt() / obfuscate() refill the obfuscator pool with this many r^n per launch when it runs dry (0 = one
 # exponentiation per call, as the reference does): 4096 rows still fit the latency geometry of one launch
 SCALAR_POOL_REFILL = 4096
+# decrypt_packed returning a LIST also goes through the unpack kernel where it can (False: lists are unpacked on the host, only
+# as_array=True takes the kernel)
+PACKED_LISTS_THROUGH_CODEC = True
 
 
 def _gpu_prime_search_available():
@@ -274,6 +277,163 @@ class PaillierPublicKey(object):
             limbs = eng.raw_encrypt_dev(m, r) if device else eng.raw_encrypt(m, r)
         return EncryptedVector(self, limbs, exps, obfuscated=fresh)
 
+    def _packed_mantissas(self, values, precision):
+        """(signed mantissas, exponent) of encrypt_packed: element-wise the int_rep and exponent that
+        EncodedNumber.encode(self, v, precision=precision) picks, all at ONE exponent (ValueError otherwise).  The mantissas come
+        back as an int64 array where numpy can make them — int arrays, float64 arrays, homogeneous lists of either — and as a
+        list of Python integers otherwise."""
+        if isinstance(values, (list, tuple)) and len(values):
+            kind = type(values[0])
+            if kind is float and all(type(v) is float for v in values):
+                values = np.array(values, dtype=np.float64)
+            elif kind is int and all(type(v) is int for v in values):
+                try:
+                    values = np.array(values, dtype=np.int64)
+                except OverflowError:
+                    pass
+        log2b = int(round(EncodedNumber.LOG2_BASE))
+        pow2_base = (1 << log2b) == EncodedNumber.BASE
+        if isinstance(values, np.ndarray):
+            arr = values.reshape(-1)
+            if arr.dtype.kind in "iu" and precision is None and (arr.dtype.kind == "i" or arr.dtype.itemsize < 8):
+                return arr.astype(np.int64), 0
+            if arr.dtype == np.float64 and pow2_base and len(arr):
+                if not np.all(np.isfinite(arr)):
+                    raise ValueError("cannot encode inf / nan")
+                if precision is not None:
+                    # one exponent for all; BASE^-exponent is a power of two, so the scaling is exact and np.rint rounds
+                    # the exact quotient half to even, as round(Fraction) does
+                    exponent = EncodedNumber._natural_exponent(0.0, precision)
+                    scaled = np.ldexp(arr, -exponent * log2b)
+                    if np.all(np.abs(scaled) < 2.0 ** 62):             # (beyond that — or inf —: element by element)
+                        return np.rint(scaled).astype(np.int64), exponent
+                elif log2b + EncodedNumber.FLOAT_MANTISSA_BITS <= 62:
+                    mag, neg, exps = EncodedNumber.encode_signed(arr)
+                    differ = np.flatnonzero(exps != exps[0])
+                    if len(differ):
+                        raise ValueError("the value at index %d encodes at exponent %d, the first at %d: give a precision"
+                                         % (differ[0], exps[differ[0]], exps[0]))
+                    rep = mag.astype(np.int64)
+                    np.negative(rep, out=rep, where=neg)
+                    return rep, int(exps[0])
+            values = arr.tolist()
+        reps, exponent = [], None
+        n, max_int = self.n, self.max_int
+        for i, v in enumerate(values):
+            e = EncodedNumber.encode(self, v, precision=precision)
+            if exponent is None:
+                exponent = e.exponent
+            elif e.exponent != exponent:
+                raise ValueError("the value at index %d encodes at exponent %d, the first at %d: give a precision"
+                                 % (i, e.exponent, exponent))
+            reps.append(e.encoding if e.encoding <= max_int else e.encoding - n)
+        return reps, (0 if exponent is None else exponent)
+
+    def _pack_plain_host(self, mantissas, slots, slot_bits):
+        """the packed plaintext rows of encrypt_packed on the host: row b = (sum_j x[b*S + j] * 2^(B j)) mod n as limb rows.
+        With u = sum_j (x_j + 2^(B-1)) 2^(B j) — B-bit fields, placed by numpy for B <= 64 — the row is (u - offset) mod n:
+        one Python integer per ROW."""
+        from . import _native
+        S, B, n = slots, slot_bits, self.n
+        count = len(mantissas)
+        rows = -(-count // S)
+        n_limbs = self._get_engine().n_limbs
+        if isinstance(mantissas, np.ndarray) and B <= 64:
+            half = 1 << (B - 1)
+            x = np.zeros(rows * S, dtype=np.int64)
+            x[:count] = mantissas
+            fields = (x.view(np.uint64) + np.uint64(half)) & np.uint64((1 << B) - 1)      # (wraps for B = 64: x ^ 2^63)
+            fields = fields.reshape(rows, S)
+            n_words = (S * B + 63) // 64 + 1
+            words = np.zeros((rows, n_words), dtype=np.uint64)
+            for j in range(S):
+                w, off = divmod(B * j, 64)
+                words[:, w] |= fields[:, j] << np.uint64(off)
+                if off + B > 64:
+                    words[:, w + 1] |= fields[:, j] >> np.uint64(64 - off)
+            offset = half * (((1 << (S * B)) - 1) // ((1 << B) - 1))
+            raw, width = words.tobytes(), 8 * n_words
+            ms = [(int.from_bytes(raw[b * width:(b + 1) * width], "little") - offset) % n for b in range(rows)]
+        else:
+            xs = mantissas.tolist() if isinstance(mantissas, np.ndarray) else mantissas
+            ms = [sum(x << (B * j) for j, x in enumerate(xs[b * S:(b + 1) * S])) % n for b in range(rows)]
+        return _native.ints_to_limbs(ms, n_limbs)
+
+    def encrypt_packed(self, values, slots, slot_bits, precision=None, r_values=None, device=False):
+        """Encode, PACK and encrypt -> EncryptedVector of ceil(len(values) / slots) rows: row b encrypts
+        V_b = x[b*S] + x[b*S + 1] * 2^B + x[b*S + 2] * 2^(2B) + ... (S = slots, B = slot_bits) for the signed mantissas x of the
+        values — what EncryptedVector.pack(S, B) makes of encrypt_batch(values), for one encryption per S values instead of S
+        encryptions and a packing step (BatchCrypt-style batching of quantised gradients; the "g, h packing" of federated
+        boosting).  Such rows add slot by slot (`+`), scale every slot (`* k`), go through segment_sum / cumsum / pack, and are
+        read back by PaillierPrivateKey.decrypt_packed(vector, S, B, count=len(values)).
+        Every value is encoded as EncodedNumber.encode(self, v, precision=precision) encodes it (signed mantissa and exponent)
+        and all exponents must agree (ValueError naming the first index that differs): integers give exponent 0, floats need a
+        `precision`.  int64 / float64 arrays and homogeneous lists are encoded by numpy with the same mantissas element for
+        element (an exact power-of-two scaling, then rounding half to even).  A mantissa outside [-2^(B-1), 2^(B-1)) raises
+        ValueError with its index.  slots / slot_bits are checked as EncryptedVector.pack checks them: not an integer —
+        TypeError, below 1 — ValueError, slots * slot_bits > max_int.bit_length() - 1 — ValueError.
+        Row b is bit for bit raw_encrypt(V_b mod n, r_b); r_values, the obfuscator pool and device=True behave as in
+        encrypt_batch.  The plaintext rows are formed on the GPU (Engine.slots_pack_dev: shifts and one reduction mod n, a
+        memory-bound kernel) and stay there; without that kernel, or for slot_bits > 64, they are formed on the host: same bits.
+        WHAT CANNOT BE CHECKED UNDER ENCRYPTION (EncryptedVector.pack): a slot whose true value, after every later addition or
+        scaling of packed vectors, leaves [-2^(B-1), 2^(B-1)) spills into its neighbour, silently.  Choosing slot_bits with
+        enough headroom for the sums to come is the caller's job."""
+        from .ciphertext import EncryptedVector
+        from ._device import DeviceArray
+        for name, value in (("slots", slots), ("slot_bits", slot_bits)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+                raise TypeError("%s must be an integer" % name)
+            if value < 1:
+                raise ValueError("%s must be at least 1" % name)
+        S, B = int(slots), int(slot_bits)
+        bound = self.max_int.bit_length() - 1
+        if S * B > bound:
+            raise ValueError("slots * slot_bits = %d bits do not fit the %d bits a plaintext of this key holds" % (S * B, bound))
+        mant, exponent = self._packed_mantissas(values, precision)
+        count = len(mant)
+        lo, hi = -(1 << (B - 1)), (1 << (B - 1)) - 1
+        if count and isinstance(mant, np.ndarray):
+            if B < 64 and (int(mant.min()) < lo or int(mant.max()) > hi):
+                i = int(np.flatnonzero((mant < lo) | (mant > hi))[0])
+                raise ValueError("the mantissa %d at index %d does not fit a slot of %d bits" % (mant[i], i, B))
+        else:
+            for i, x in enumerate(mant):
+                if not lo <= x <= hi:
+                    raise ValueError("the mantissa %d at index %d does not fit a slot of %d bits" % (x, i, B))
+        eng = self._get_engine()
+        rows = -(-count // S)
+        exps = np.full(rows, exponent, dtype=np.int64)
+        fresh = r_values is None
+        if rows == 0:
+            empty = DeviceArray(eng.ctx, 0, eng.ct_limbs) if device else np.zeros((0, eng.ct_limbs), dtype=np.uint32)
+            return EncryptedVector(self, empty, exps, obfuscated=fresh)
+        resident = isinstance(mant, np.ndarray) and B <= 64 and eng.has_slot_codec()
+        m = eng.slots_pack_dev(mant, S, B) if resident else self._pack_plain_host(mant, S, B)
+        limbs = None
+        if fresh and hasattr(eng.ctx, "encrypt_dev"):
+            limbs = eng.encrypt_from_obfuscators(m)                 # the pool made by precompute_obfuscators (each used once)
+            if limbs is None and rows <= SCALAR_POOL_REFILL // 4:
+                eng.fill_obfuscator_pool(SCALAR_POOL_REFILL)
+                limbs = eng.encrypt_from_obfuscators(m)
+            if limbs is None:
+                limbs = eng.raw_encrypt_fresh(m, device)
+            elif not device:
+                limbs = limbs.to_host()
+        else:
+            if fresh:
+                r = random_lt_n_limbs(self.n, rows, eng.n_limbs)
+            else:
+                r = r_values if isinstance(r_values, np.ndarray) else list(r_values)
+                if len(r) != rows:
+                    raise ValueError("%d r_values for %d packed rows" % (len(r), rows))
+            if device or resident:
+                limbs = eng.raw_encrypt_dev(m, r)
+                if not device:
+                    limbs = limbs.to_host()
+            else:
+                limbs = eng.raw_encrypt(m, r)
+        return EncryptedVector(self, limbs, exps, obfuscated=fresh)
+
     def encrypt_batch_sharded(self, values, precision=None):
         """encrypt_batch with the ciphertexts left RESIDENT, one EncryptedVector per device of the fleet (contiguous shards in
         order; a single vector on the ordinary device when no fleet is configured): the per-device list form of the fan-out.
@@ -493,7 +653,7 @@ class PaillierPrivateKey(object):
         elif len(vector):
             yield 0, len(vector), eng.raw_decrypt(limbs)
 
-    def decrypt_packed(self, vector, slots, slot_bits, count=None, Encoding=None):
+    def decrypt_packed(self, vector, slots, slot_bits, count=None, Encoding=None, as_array=False):
         """The values of a vector packed by EncryptedVector.pack(slots, slot_bits) (and of sums of such vectors) -> list of
         decoded ints / floats, like decrypt_batch: ONE decrypt per `slots` values.  Value number b * slots + j is slot j of
         row b.  The rows are decrypted through the raw decrypt paths of decrypt_batch; each plaintext m is unpacked on the host:
@@ -502,6 +662,12 @@ class PaillierPrivateKey(object):
         (OverflowError: the packed value did not fit slots * slot_bits bits).  d_j is decoded as
         Encoding(public_key, d_j % n, exponent of row b).decode().  count keeps the first `count` values (default
         len(vector) * slots; outside [0, len(vector) * slots]: ValueError).
+        as_array=True returns a numpy array instead of the list — np.int64 when every exponent is 0, np.float64 when every
+        exponent is negative, cut to `count` — and raises ValueError where that form does not apply: slot_bits > 64, a custom
+        Encoding, or exponents of both kinds.
+        With the slot codec kernels (Engine.has_slot_codec), slot_bits <= 64, the default Encoding and exponents of one kind,
+        the unpack kernel runs behind each chunk's decrypt (Engine.raw_decrypt_unpack_chunks): int64 values and one status byte
+        per row come down instead of limb rows.  Same values, same exceptions, and the lowest row index decides which is raised.
         A slot that left [-2^(B-1), 2^(B-1)) before it was decrypted has spilled into its neighbour and cannot be told from a
         legitimate value: see EncryptedVector.pack."""
         from .ciphertext import EncryptedVector
@@ -524,17 +690,52 @@ class PaillierPrivateKey(object):
         if not 0 <= count <= total:
             raise ValueError("count must lie in [0, %d]" % total)
         plain_decode = Encoding is None or Encoding is EncodedNumber
-        out, exps = [], vector.exponent_array
+        exps = vector.exponent_array
+        all_int, all_float = bool((exps == 0).all()), bool(len(exps) and (exps < 0).all())
+        if as_array:
+            if slot_bits > 64:
+                raise ValueError("as_array needs slot_bits <= 64: a wider slot does not fit int64")
+            if not plain_decode:
+                raise ValueError("as_array does not apply to a custom Encoding")
+            if not (all_int or all_float):
+                raise ValueError("as_array needs exponents that are all 0 (int64) or all negative (float64)")
+        log2b = int(round(EncodedNumber.LOG2_BASE))
+        eng = self._get_engine()
+        fl = self._get_fleet()
+        if vector.on_device and fl is not None:
+            eng = self.public_key._engine_for(vector._store)
+        fanned_out = not vector.on_device and fl is not None and len(fl.shards(len(vector))) > 1
+        if (len(vector) and plain_decode and slot_bits <= 64 and (all_int or all_float) and (1 << log2b) == EncodedNumber.BASE
+                and int(exps.min()) * log2b >= -960 and not fanned_out and eng.has_slot_codec()
+                and (as_array or PACKED_LISTS_THROUGH_CODEC)):
+            parts = []
+            for lo, hi, values, status in eng.raw_decrypt_unpack_chunks(vector.limbs(be_secure=False), slots, slot_bits):
+                bad = np.flatnonzero(status)
+                if len(bad):
+                    if status[bad[0]] == 1:
+                        raise OverflowError('Overflow detected in decrypted number')
+                    raise OverflowError('a packed value does not fit %d slots of %d bits' % (slots, slot_bits))
+                parts.append(values)
+            vals = (parts[0] if len(parts) == 1 else np.concatenate(parts))[:count]
+            if all_float:
+                # correctly rounded int64 -> float64, then an exact power-of-two scaling = the reference's true division
+                vals = np.ldexp(vals.astype(np.float64), np.repeat(exps, slots)[:count] * log2b)
+            return vals if as_array else vals.tolist()
+        out = []
         for lo, hi, plain in self._raw_plain_chunks(vector):
-            out += self._unpack_plain(plain, exps[lo:hi], slots, slot_bits, None if plain_decode else Encoding)
+            out.append(self._unpack_plain(plain, exps[lo:hi], slots, slot_bits, None if plain_decode else Encoding, as_array))
+        if as_array:
+            out = [np.asarray(part, dtype=np.int64 if all_int else np.float64) for part in out]
+            return np.concatenate(out)[:count] if out else np.zeros(0, dtype=np.int64 if all_int else np.float64)
+        out = [x for part in out for x in part]
         del out[count:]
         return out
 
-    def _unpack_plain(self, plain, exps, slots, slot_bits, Encoding):
+    def _unpack_plain(self, plain, exps, slots, slot_bits, Encoding, as_array=False):
         """the decoded slots of the plaintext rows `plain` (host limbs), row after row (decrypt_packed).  With
         u = v + sum_j 2^(B-1) 2^(B j) the slots are the B-bit digits of u less 2^(B-1), and v fits slots * B bits exactly when
         0 <= u < 2^(slots * B): one Python integer per ROW; for B <= 64 the digits are cut out of the rows' 64-bit words by
-        numpy, `slots` vector operations whatever the number of rows."""
+        numpy, `slots` vector operations whatever the number of rows (as_array: those values as the numpy array they are)."""
         from . import _native
         pk = self.public_key
         n, max_int = pk.n, pk.max_int
@@ -578,8 +779,8 @@ class PaillierPrivateKey(object):
             vals = vals.reshape(-1)
             if row_exps[0] < 0:
                 # correctly rounded int64 -> float64, then an exact power-of-two scaling = the reference's true division
-                return np.ldexp(vals.astype(np.float64), row_exps * log2b).tolist()
-            return vals.tolist()
+                vals = np.ldexp(vals.astype(np.float64), row_exps * log2b)
+            return vals if as_array else vals.tolist()
         mask = (1 << B) - 1
         cls = EncodedNumber if Encoding is None else Encoding
         out = []
