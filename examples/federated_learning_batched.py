@@ -102,12 +102,16 @@ def run_scalar(key_length=2048, n_rounds=N_ROUNDS, verbose=True, keypair=None):
     return errors, elapsed, calls
 
 
-def run(key_length=2048, n_rounds=N_ROUNDS, verbose=True, precompute=False):
+def run(key_length=2048, n_rounds=N_ROUNDS, verbose=True, precompute=False, short_obfuscators=False):
     """precompute=True: the obfuscators r^n of every encryption of the run are made ahead of time in ONE launch
     (PaillierPublicKey.precompute_obfuscators: the offline half of Paillier encryption); the rounds then only pay the
-    online product per gradient entry.  The decrypted aggregates — hence the models — are the same either way."""
+    online product per gradient entry.  short_obfuscators=True: every obfuscator is h_s^rho for a short random rho
+    (PaillierPublicKey.enable_short_obfuscators: a table look-up and a product per exponent digit instead of the
+    exponentiation r^n).  The decrypted aggregates — hence the models — are the same either way."""
     parts, X_test, y_test = load_split(N_HOSPITALS)
     public_key, private_key = paillier.generate_paillier_keypair(n_length=key_length)
+    if short_obfuscators:
+        public_key.enable_short_obfuscators()
     hospitals = [Hospital(X, y, public_key) for X, y in parts]
     if precompute and hasattr(public_key, "precompute_obfuscators") and hasattr(public_key._get_engine().ctx, "encrypt_dev"):
         t_off = time.perf_counter()
@@ -125,7 +129,8 @@ def run(key_length=2048, n_rounds=N_ROUNDS, verbose=True, precompute=False):
     elapsed = time.perf_counter() - t0
     errors = [h.test_error(X_test, y_test) for h in hospitals]
     if verbose:
-        print("federated rounds: %d, key: %d bits, %.1f s" % (n_rounds, key_length, elapsed))
+        print("federated rounds%s: %d, key: %d bits, %.1f s"
+              % (" (short-exponent obfuscators)" if short_obfuscators else "", n_rounds, key_length, elapsed))
         for i, e in enumerate(errors, 1):
             print("Hospital %d:\t%.2f" % (i, e))
     return errors, elapsed
@@ -180,5 +185,6 @@ if __name__ == "__main__":
     print("local-only test MSE:", ", ".join("%.2f" % e for e in local_only()))
     run(bits)
     run(bits, precompute=True)
+    run(bits, short_obfuscators=True)
     run_packed(bits)
     run_scalar(bits)

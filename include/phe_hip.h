@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 10
+#define PHE_HIP_ABI_VERSION 11
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -315,6 +315,27 @@ int phe_hip_slots_pack_dev(phe_hip_ctx* ctx, const int64_t* values, size_t count
                            uint32_t* m_rows, size_t rows, void* stream);
 int phe_hip_slots_unpack_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t rows, uint32_t slots, uint32_t slot_bits,
                              int64_t* values, uint8_t* status, void* stream);
+/* Powers of ONE base by many short exponents (csrc/fixed_base.h): the short-exponent obfuscators h_s^rho of
+ * PaillierPublicKey.enable_short_obfuscators.  A fixed-base comb: with the exponent cut into T = ceil(exp_bits / window) digits,
+ * hs^e is the product of T entries of a table of T * (2^window - 1) pair rows, entry (t, d) = hs^(d * 2^(window t)) at row
+ * t * (2^window - 1) + d - 1 — T pair products and no squaring.
+ * set: builds the table on the device from hs (ct_limbs words on the HOST, a residue mod n^2) for exponents below 2^exp_bits
+ * (1 <= exp_bits <= 32 * n_limbs); window 0: the library's choice for the key width, else 1 .. 12 (clamped to exp_bits).  It
+ * replaces a table set before and stays until the next set, clear, or the end of the context.  Once per key: not a hot path.
+ * info: what is set (all zero when nothing is).  clear: frees the table.  rows_dev: copies `count` table rows from row `first`
+ * on to `out` (pair rows on the device).
+ * pow_dev: out[i] = mul[i] * hs^e[i] for e: (batch, exp_limbs) words on the device, exp_limbs == ceil(exp_bits / 32); bits of
+ * e[i] at or above exp_bits are not read.  mul: NULL (1), pair rows (mul_is_pair) or canonical residues of ct_limbs words,
+ * converted as they are read.  out_is_pair: `out` receives pair rows; else canonical residues, times (1 + n*m[i]) when m
+ * ((batch, n_limbs) plaintext rows) is given: with mul == NULL that is raw_encrypt(m[i], r_value = h^e[i] mod n) of
+ * phe/paillier.py:102-139 for hs = h^n.  EINVAL: no table, no split-modulus engine, another exp_limbs, m with out_is_pair, a
+ * null buffer. */
+int phe_hip_fixed_base_set(phe_hip_ctx* ctx, const uint32_t* hs, int exp_bits, int window);
+int phe_hip_fixed_base_info(const phe_hip_ctx* ctx, int* exp_bits, int* window, int* positions, size_t* table_bytes);
+int phe_hip_fixed_base_clear(phe_hip_ctx* ctx);
+int phe_hip_fixed_base_rows_dev(phe_hip_ctx* ctx, size_t first, size_t count, uint32_t* out_pair, void* stream);
+int phe_hip_fixed_base_pow_dev(phe_hip_ctx* ctx, const uint32_t* e, int exp_limbs, const uint32_t* mul, int mul_is_pair,
+                               const uint32_t* m, uint32_t* out, int out_is_pair, size_t batch, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

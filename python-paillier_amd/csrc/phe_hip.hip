@@ -32,6 +32,7 @@
 #include "split_core.h"
 #include "segment_core.h"
 #include "slot_codec.h"
+#include "fixed_base.h"
 #include "mul_io.h"
 #include "mul_table.h"
 #include "decrypt_tail.h"
@@ -131,6 +132,9 @@ namespace slots {  // kernels_slots.hip
 int launch_slots_pack(int G, int K, int blocks, hipStream_t st, const SlotPackArgs& A);
 int launch_slots_unpack(int G, int K, int blocks, hipStream_t st, const SlotUnpackArgs& A);
 }  // namespace slots
+namespace fb {  // kernels_fb.hip
+int launch_fixed_base_pow(int G, int L, int blocks, hipStream_t st, const FixedBaseArgs& A, bool mul_is_residue, bool exit);
+}  // namespace fb
 }  // namespace phe
 
 namespace phe {
@@ -428,6 +432,11 @@ struct phe_hip_ctx {
     // the constant rows of the slot codec (slot_codec.h host::slot_const_rows), one device block per (slots, slot_bits) seen
     struct SlotRows { uint32_t slots, slot_bits; uint32_t* dev; };
     std::vector<SlotRows> slot_rows;
+    // the comb table of the fixed base (fixed_base.h; phe_hip_fixed_base_set): fb_positions * (2^fb_window - 1) pair rows, kept
+    // until the base changes, phe_hip_fixed_base_clear, or the context goes; nullptr: no base set
+    uint32_t* fb_table = nullptr;
+    int fb_bits = 0, fb_window = 0, fb_positions = 0;
+    size_t fb_bytes = 0;
     // grow-only device scratch
     uint32_t* table = nullptr;
     size_t table_words = 0;
@@ -1478,7 +1487,7 @@ void phe_hip_ctx_destroy(phe_hip_ctx* ctx) {
                         ctx->d_nsq.blob, ctx->d_psq.blob, ctx->d_qsq.blob, ctx->d_exp_n.ops, ctx->d_exp_p.ops,
                         ctx->d_exp_q.ops, ctx->d_tail.blob, ctx->table, ctx->table2, ctx->scratch, ctx->partial, ctx->lookup, (uint32_t*)ctx->flags, ctx->stage[0],
                         ctx->stage[1], ctx->stage[2], ctx->owner_blob, ctx->d_nunit.blob, ctx->unit_tmp, ctx->tail_wave_blob, ctx->item_sched,
-                        ctx->tmul_blob, ctx->tmul_cols};
+                        ctx->tmul_blob, ctx->tmul_cols, ctx->fb_table};
     for (const auto& R : ctx->pub_rungs) { bufs.push_back(R.nsq.blob); bufs.push_back(R.nsplit.blob); bufs.push_back(R.nunit.blob); }
     for (const auto& R : ctx->priv_rungs) { bufs.push_back(R.psq.blob); bufs.push_back(R.qsq.blob); bufs.push_back(R.psplit.blob); bufs.push_back(R.qsplit.blob); }
     for (const auto& R : ctx->slot_rows) bufs.push_back(R.dev);
@@ -2179,6 +2188,167 @@ int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_ar
     ctx->last_geom_pub = geom_code(sp.G, sp.L);
     const int blocks = grid_blocks(ctx, tasks, sp.G, 2);
     if (phe::seg::launch_segment_pack(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// ---- powers of one fixed base by short exponents (fixed_base.h, kernels_fb.hip) -----------------------------------------------
+// The window the library picks (window = 0 in phe_hip_fixed_base_set): the widest one, up to kFixedBaseMaxWindow, whose table
+// stays within kFixedBaseTableBytes.  The kernel's time follows the number of positions T = ceil(bits / w) and nothing else — the
+// gathered table rows cost nothing measurable up to the 453 MB tried — so the widest window wins at every key width measured
+// (tools/bench_short_obfuscators.py; DESIGN.md "Short-exponent obfuscators": 12 at 1024, 2048 and 3072 bits); every further bit
+// doubles the table and the time to build it for under a tenth fewer products, which is what the two bounds are for.
+constexpr size_t kFixedBaseTableBytes = (size_t)512 << 20;
+static int fixed_base_default_window(int exp_bits, size_t row_bytes) {
+    for (int w = phe::kFixedBaseMaxWindow; w > 1; --w) {
+        const size_t T = ((size_t)exp_bits + w - 1) / w;
+        if (T * (((size_t)1 << w) - 1) * row_bytes <= kFixedBaseTableBytes) return w;
+    }
+    return 1;
+}
+static int fixed_base_drop(phe_hip_ctx* ctx) {
+    if (ctx->fb_table) {
+        HIP_TRY(hipDeviceSynchronize());  // nothing may still read the table
+        (void)hipFree(ctx->fb_table);
+    }
+    ctx->fb_table = nullptr;
+    ctx->fb_bits = ctx->fb_window = ctx->fb_positions = 0;
+    ctx->fb_bytes = 0;
+    return PHE_HIP_OK;
+}
+
+// table[t][d] = hs^(d * 2^(w t)) as pair rows: hs into the pair form (to_pair), one copy of it per entry, every entry to its own
+// power by the per-row exponentiation on pair rows (pair_powmod).  Once per key and base: not a hot path.
+int phe_hip_fixed_base_set(phe_hip_ctx* ctx, const uint32_t* hs, int exp_bits, int window) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (!hs) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (exp_bits < 1 || exp_bits > 32 * ctx->pub.s1) return fail(PHE_HIP_EINVAL, "exp_bits must lie in [1, 32 * n_limbs]");
+    if (window < 0 || window > phe::kFixedBaseMaxWindow)
+        return fail(PHE_HIP_EINVAL, "window must lie in [0, " + std::to_string(phe::kFixedBaseMaxWindow) + "]");
+    if (int rc = bind_device(ctx)) return rc;
+    if (!(ctx->use_split && ctx->d_nsplit.G)) return fail(PHE_HIP_EINVAL, "the pair form needs the split-modulus engine");
+    if (window == 0) window = fixed_base_default_window(exp_bits, (size_t)8 * ctx->d_nsplit.H);
+    if (window > exp_bits) window = exp_bits;
+    const int T = (exp_bits + window - 1) / window;
+    const size_t per_pos = ((size_t)1 << window) - 1, rows = (size_t)T * per_pos;
+    const size_t s2 = (size_t)ctx->pub.s2, w2 = (size_t)2 * ctx->d_nsplit.H;
+    const int el = (T * window + 31) / 32;  // words of the largest exponent, (2^w - 1) * 2^(w (T - 1))
+    if (int rc = fixed_base_drop(ctx)) return rc;
+    uint32_t *d_hs = nullptr, *d_one = nullptr, *d_src = nullptr, *d_e = nullptr, *d_tab = nullptr;
+    auto cleanup = [&]() {
+        for (uint32_t* b : {d_hs, d_one, d_src, d_e})
+            if (b) (void)hipFree(b);
+    };
+    auto build = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_hs, s2 * 4));
+        HIP_TRY(hipMalloc(&d_one, w2 * 4));
+        HIP_TRY(hipMalloc(&d_src, rows * w2 * 4));
+        HIP_TRY(hipMalloc(&d_e, rows * (size_t)el * 4));
+        HIP_TRY(hipMalloc(&d_tab, rows * w2 * 4));
+        HIP_TRY(hipMemcpy(d_hs, hs, s2 * 4, hipMemcpyHostToDevice));
+        {
+            PHE_CTX_ORDER(ctx, nullptr);
+            if (int rc = pair_launch(ctx, 0, d_hs, nullptr, 0, 0, d_one, 1, nullptr)) return rc;
+        }
+        std::vector<uint32_t> one(w2), src(rows * w2), e(rows * (size_t)el, 0u);
+        HIP_TRY(hipMemcpy(one.data(), d_one, w2 * 4, hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < rows; ++r) {
+            std::copy(one.begin(), one.end(), src.begin() + r * w2);
+            const uint64_t d = r % per_pos + 1;
+            const size_t bit = (r / per_pos) * (size_t)window;  // the exponent d << bit (d < 2^12: at most two words)
+            const uint64_t v = d << (bit & 31);
+            e[r * el + (bit >> 5)] = (uint32_t)v;
+            if ((v >> 32) != 0) e[r * el + (bit >> 5) + 1] = (uint32_t)(v >> 32);
+        }
+        HIP_TRY(hipMemcpy(d_src, src.data(), rows * w2 * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_e, e.data(), rows * (size_t)el * 4, hipMemcpyHostToDevice));
+        {
+            PHE_CTX_ORDER(ctx, nullptr);
+            const DevSplit& sp = pick_pair_split(ctx, rows);
+            if (int rc = launch_var_split(ctx, sp, d_src, 0, d_e, el, T * window, d_tab, 0, rows, nullptr, true)) return rc;
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        return PHE_HIP_OK;
+    };
+    const int rc = build();
+    cleanup();
+    if (rc) {
+        if (d_tab) (void)hipFree(d_tab);
+        return rc;
+    }
+    ctx->fb_table = d_tab;
+    ctx->fb_bits = exp_bits;
+    ctx->fb_window = window;
+    ctx->fb_positions = T;
+    ctx->fb_bytes = rows * w2 * 4;
+    return PHE_HIP_OK;
+}
+
+int phe_hip_fixed_base_info(const phe_hip_ctx* ctx, int* exp_bits, int* window, int* positions, size_t* table_bytes) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (exp_bits) *exp_bits = ctx->fb_bits;
+    if (window) *window = ctx->fb_window;
+    if (positions) *positions = ctx->fb_positions;
+    if (table_bytes) *table_bytes = ctx->fb_bytes;
+    return PHE_HIP_OK;
+}
+
+int phe_hip_fixed_base_clear(phe_hip_ctx* ctx) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (int rc = bind_device(ctx)) return rc;
+    return fixed_base_drop(ctx);
+}
+
+// copies `count` rows of the table, from row `first` on, to `out` (pair rows, device): what tests and tools read entries by
+int phe_hip_fixed_base_rows_dev(phe_hip_ctx* ctx, size_t first, size_t count, uint32_t* out, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (!ctx->fb_table) return fail(PHE_HIP_EINVAL, "no fixed base is set");
+    const size_t w2 = (size_t)2 * ctx->d_nsplit.H, rows = ctx->fb_bytes / (w2 * 4);
+    if (first > rows || count > rows - first) return fail(PHE_HIP_EINVAL, "rows beyond the table");
+    if (count == 0) return PHE_HIP_OK;
+    if (!out) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    HIP_TRY(hipMemcpyAsync(out, ctx->fb_table + first * w2, count * w2 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PHE_HIP_OK;
+}
+
+// out[i] = mul[i] * hs^e[i] (* (1 + n*m[i])) by the comb over the table (fixed_base.h fixed_base_pow_body): one table look-up and
+// one pair product per exponent digit, no squaring.  The geometry is the pair rung of `batch` limb groups.
+int phe_hip_fixed_base_pow_dev(phe_hip_ctx* ctx, const uint32_t* e, int exp_limbs, const uint32_t* mul, int mul_is_pair,
+                               const uint32_t* m, uint32_t* out, int out_is_pair, size_t batch, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (!(ctx->use_split && ctx->d_nsplit.G)) return fail(PHE_HIP_EINVAL, "the pair form needs the split-modulus engine");
+    if (!ctx->fb_table) return fail(PHE_HIP_EINVAL, "no fixed base is set");
+    if (exp_limbs != (ctx->fb_bits + 31) / 32)
+        return fail(PHE_HIP_EINVAL, "exp_limbs must be " + std::to_string((ctx->fb_bits + 31) / 32) + " for exponents of " +
+                                        std::to_string(ctx->fb_bits) + " bits");
+    if (m && out_is_pair) return fail(PHE_HIP_EINVAL, "a plaintext row is folded in on the way out of the pair form only");
+    if (batch == 0) return PHE_HIP_OK;
+    if (!e || !out) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    const DevSplit& sp = pick_pair_split(ctx, batch);
+    FixedBaseArgs A;
+    A.mod = sp.c;
+    A.table = ctx->fb_table;
+    A.e = e;
+    A.exp_limbs = exp_limbs;
+    A.exp_bits = ctx->fb_bits;
+    A.window = ctx->fb_window;
+    A.positions = ctx->fb_positions;
+    A.mul = mul;
+    A.m = m;
+    A.m_limbs = ctx->pub.s1;
+    A.out = out;
+    A.limbs = ctx->pub.s2;
+    A.chunks = chunks_for(ctx->pub.s2, sp.rows);
+    A.batch = batch;
+    ctx->last_path = 0;
+    ctx->last_geom_pub = geom_code(sp.G, sp.L);
+    const int blocks = grid_blocks(ctx, batch, sp.G, 2);
+    if (phe::fb::launch_fixed_base_pow(sp.G, sp.L, blocks, (hipStream_t)stream, A, mul && !mul_is_pair, !out_is_pair) < 0)
         return fail(PHE_HIP_EINVAL, "unsupported split geometry");
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;

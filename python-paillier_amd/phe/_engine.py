@@ -106,6 +106,26 @@ def random_lt_n_limbs(n, count, limbs, out=None):
         out[rows] = fresh
 
 
+def random_bits_limbs(bits, count, limbs, out=None):
+    """`count` cryptographically random integers in [0, 2^bits) as a (count, limbs) uint32 array: the short exponents rho of
+    the short-exponent obfuscators (Engine.set_short_base), from the same kernel CSPRNG as random_lt_n_limbs — every value of
+    the range is a valid exponent, so nothing is redrawn.  `out`: optional (count, limbs) uint32 array to fill."""
+    bits, limbs = int(bits), int(limbs)
+    if bits < 1 or bits > 32 * limbs:
+        raise ValueError("bits must lie in [1, %d]" % (32 * limbs))
+    if out is None:
+        out = np.empty((count, limbs), dtype=np.uint32)
+    if count == 0:
+        return out
+    _urandom_into(out)
+    top_limb, top_bits = (bits - 1) // 32, bits - 32 * ((bits - 1) // 32)
+    if top_bits < 32:
+        out[:, top_limb] &= np.uint32((1 << top_bits) - 1)
+    if top_limb + 1 < limbs:
+        out[:, top_limb + 1:] = 0
+    return out
+
+
 class ObfuscatorPool:
     """Obfuscators r^n mod n^2 made ahead of time, each handed out ONCE (two ciphertexts sharing one reveal m1 - m2).
     The pool is an object of its own with its own lock because it outlives the engine it was filled through: when a key
@@ -680,19 +700,27 @@ class Engine:
         resident = isinstance(m, DeviceArray)
         count = m.rows if resident else m.shape[0]
         st = self._launch_stream()
+        short = self.short_base()
+        el = (short[1] + 31) // 32 if short else 0
         out = DeviceArray(self.ctx, count, self.ct_limbs)
         host = None if device else np.empty((count, self.ct_limbs), dtype=np.uint32)
         keep = []                                         # operand buffers stay alive until the final sync
         lo, chunk, prev = 0, 1 << 15, None                # chunks are multiples of the groups in flight (32768 at 2048 bits)
         while lo < count:
             hi = min(count, lo + chunk)
-            r = random_lt_n_limbs(self.n, hi - lo, self.n_limbs, out=self.scratch("r", hi - lo, self.n_limbs))
+            if short:                                     # short-exponent obfuscators: rho instead of r, h_s^rho instead of r^n
+                r = random_bits_limbs(short[1], hi - lo, el, out=self.scratch("rho", hi - lo, el))
+            else:
+                r = random_lt_n_limbs(self.n, hi - lo, self.n_limbs, out=self.scratch("r", hi - lo, self.n_limbs))
             m_d = m.rows_view(lo, hi) if resident else DeviceArray.from_host(self.ctx, m[lo:hi])
             r_d = DeviceArray.from_host(self.ctx, r)      # synchronous copy: the scratch buffer is free again
             keep += [m_d, r_d]
             if host is not None and st:
                 self.ctx.sync(st)                         # the previous chunk is complete (its successor starts right away)
-            self._encrypt_dev(m_d.ptr, r_d.ptr, out.rows_view(lo, hi).ptr, hi - lo, st)
+            if short:
+                self._short_launch(r_d, None, False, m_d, out.rows_view(lo, hi), False, st, keep)
+            else:
+                self._encrypt_dev(m_d.ptr, r_d.ptr, out.rows_view(lo, hi).ptr, hi - lo, st)
             if host is not None and st and prev is not None:
                 self.ctx.d2h(host[prev[0]:prev[1]], out.rows_view(*prev).ptr)     # download under this chunk's kernel
             prev = (lo, hi)
@@ -714,6 +742,10 @@ class Engine:
         rows of the engine's pair form where it has one: the online part of an encryption is then one exit from that form
         with the plaintext folded in (Engine.encrypt_from_obfuscators)"""
         if count <= 0:
+            return self.obfuscators_available()
+        if self.short_base():
+            # short-exponent obfuscators h_s^rho: the comb leaves pair rows directly (no exit and no conversion back)
+            self._obf.add(self.short_fresh_dev(count, want_pair=bool(self.pair_form())))
             return self.obfuscators_available()
         zeros = np.zeros((count, self.n_limbs), dtype=np.uint32)
         block = self.raw_encrypt_fresh(zeros, device=True)
@@ -1047,6 +1079,8 @@ class Engine:
         chunk under the kernels of the current one).  rows: indices that get a fresh r (None = all); the others get
         r = 1 (c * 1^n = c, still canonical)."""
         count = c.rows
+        if self.short_base():
+            return self.short_fresh_dev(count, mul=c, rows=rows)
         st = self._launch_stream()
         need = None
         if rows is not None:
@@ -1069,6 +1103,158 @@ class Engine:
             r_d = DeviceArray.from_host(self.ctx, r)
             keep.append(r_d)
             self._obfuscate_dev(c.rows_view(lo, hi).ptr, r_d.ptr, out.rows_view(lo, hi).ptr, hi - lo, st)
+            lo, chunk = hi, 1 << 16
+        self.ctx.sync(st)
+        return out
+
+    # ---- short-exponent obfuscators: h_s^rho for a fixed h_s = h^n mod n^2 and short random rho (csrc/fixed_base.h) -------------
+    # With h = -x^2 mod n, h_s^rho = (h^rho)^n is an n-th power like r^n, so it blinds a ciphertext the same way and decrypts the
+    # same; c = (1 + n m) * h_s^rho is bit for bit raw_encrypt(m, r_value = h^rho mod n) (phe/paillier.py:102-139).  The base is
+    # the same for every row: a fixed-base comb over a table kept by the native context, ceil(bits / w) pair products per row and
+    # no squaring (include/phe_hip.h phe_hip_fixed_base_pow_dev).  The setting is the key's (PaillierPublicKey
+    # .enable_short_obfuscators); every engine of the key is told it and builds its own table on first use.
+    def short_base(self):
+        """(h_s, bits) while short-exponent obfuscators are on, else None"""
+        return self.__dict__.get("_short")
+
+    def set_short_base(self, hs, bits=0):
+        """draw every fresh obfuscator as hs^rho, rho uniform in [0, 2^bits), from now on (hs None: r^n again).  The table of a
+        base set before is dropped; the new one is built when the kernel first needs it."""
+        if self.__dict__.get("_short_table"):
+            self.ctx.fixed_base_clear()
+        self._short_table = False
+        self._short_rows = None
+        if hs is None:
+            self._short = None
+            return
+        hs, bits = int(hs), int(bits)
+        if not 1 < hs < self.nsquare:
+            raise ValueError("h_s must lie in (1, n^2)")
+        if not 1 <= bits <= self.n.bit_length():
+            raise ValueError("bits must lie in [1, %d]" % self.n.bit_length())
+        self._short = (hs, bits)
+
+    def has_fixed_base(self):
+        """True when h_s^rho has its kernel: a base is set, the pair form is offered and the backend has the entry points"""
+        return self.short_base() is not None and bool(self.pair_form()) and hasattr(self.ctx, "fixed_base_pow_dev")
+
+    def _short_table_ready(self):
+        if not self.__dict__.get("_short_table"):
+            hs, bits = self._short
+            self.ctx.fixed_base_set(hs, bits, int(os.environ.get("PHE_HIP_SHORT_WINDOW", "0") or 0))
+            self._short_table = True
+
+    def short_table_info(self):
+        """{"bits", "window", "positions", "table_bytes"} of the comb table (built now if it was not yet); all 0 without the
+        kernel"""
+        if not self.has_fixed_base():
+            return {"bits": 0, "window": 0, "positions": 0, "table_bytes": 0}
+        self._short_table_ready()
+        return self.ctx.fixed_base_info()
+
+    def short_table_rows_dev(self, first, count):
+        """`count` rows of the comb table from row `first` on, as pair rows (entry (t, d) is row t * (2^window - 1) + d - 1)"""
+        self._short_table_ready()
+        out = DeviceArray(self.ctx, count, self.pair_form())
+        self.ctx.fixed_base_rows_dev(first, count, out.ptr)
+        self.ctx.sync()
+        return out
+
+    def _short_launch(self, e, mul, mul_is_pair, m, out, out_is_pair, st, keep):
+        """queue out[i] = mul[i] * h_s^e[i] (* (1 + n*m[i])) on stream `st` (all operands resident; m only with canonical
+        output): the comb kernel, or — without it — the composition of existing calls: powmod of the broadcast h_s by e, raw_add
+        with mul, add_plain with m.  Same canonical residues either way.  Temporaries are appended to `keep`."""
+        hs, bits = self._short
+        el, rows = (bits + 31) // 32, e.rows
+        if e.cols != el:
+            raise ValueError("exponents of %d bits come as rows of %d words, not %d" % (bits, el, e.cols))
+        if m is not None and out_is_pair:
+            raise ValueError("a plaintext is folded in on the way out of the pair form only")
+        if self.has_fixed_base():
+            self._short_table_ready()
+            self.ctx.fixed_base_pow_dev(e.ptr, el, mul.ptr if mul is not None else None, mul_is_pair,
+                                        m.ptr if m is not None else None, out.ptr, out_is_pair, rows, st)
+            return
+        base = self.__dict__.get("_short_rows")
+        if base is None or base.rows < rows:
+            base = self._short_rows = DeviceArray.from_host(self.ctx, np.tile(self.cipher_limbs([hs]), (max(rows, 1 << 12), 1)))
+        cur = out if not (out_is_pair or mul is not None or m is not None) else DeviceArray(self.ctx, rows, self.ct_limbs)
+        self.ctx.powmod_dev(base.ptr, e.ptr, el, bits, cur.ptr, rows, st)
+        keep += [base, cur]
+        if mul is not None:
+            if mul_is_pair:
+                plain = DeviceArray(self.ctx, rows, self.ct_limbs)
+                self.ctx.from_pair_dev(mul.ptr, None, plain.ptr, rows, st)
+                keep.append(plain)
+                mul = plain
+            nxt = out if not (out_is_pair or m is not None) else DeviceArray(self.ctx, rows, self.ct_limbs)
+            self.ctx.mulmod_dev(mul.ptr, cur.ptr, nxt.ptr, rows, st)
+            keep.append(nxt)
+            cur = nxt
+        if m is not None:
+            self.ctx.add_plain_dev(cur.ptr, m.ptr, out.ptr, rows, st)
+        elif out_is_pair:
+            self.ctx.to_pair_dev(cur.ptr, out.ptr, rows, st)
+
+    def short_pow_dev(self, rho, mul=None, mul_is_pair=False, m=None, want_pair=False):
+        """out[i] = mul[i] * h_s^rho[i] (* (1 + n*m[i])) on resident rows.  rho: (count, ceil(bits / 32)) uint32 rows, host or
+        resident; mul: None (1), resident pair rows (mul_is_pair) or canonical residues; m: plaintext limb rows, host or resident
+        (canonical output only).  Returns canonical residues, or pair rows (want_pair)."""
+        e = rho if isinstance(rho, DeviceArray) else DeviceArray.from_host(self.ctx, rho)
+        if m is not None and not isinstance(m, DeviceArray):
+            m = self.upload_plain([v % self.n for v in m] if not isinstance(m, np.ndarray) else m)
+        for name, other in (("mul", mul), ("m", m)):
+            if other is not None and other.rows != e.rows:
+                raise ValueError("%d rows of %s for %d exponents" % (other.rows, name, e.rows))
+        out = DeviceArray(self.ctx, e.rows, self.pair_form() if want_pair else self.ct_limbs)
+        if e.rows:
+            keep = []
+            self._short_launch(e, mul, mul_is_pair, m, out, want_pair, 0, keep)
+            self.ctx.sync()
+        return out
+
+    def short_pow(self, rho, mul=None, m=None):
+        """short_pow_dev for host rows (rho and mul: limb rows, m: limb rows or Python ints), host rows out; on a backend
+        without resident rows the same composition through its host entry points"""
+        rho = np.ascontiguousarray(rho, dtype=np.uint32)
+        if m is not None and not isinstance(m, np.ndarray):
+            m = self.plain_limbs([v % self.n for v in m])
+        if hasattr(self.ctx, "powmod_dev"):
+            mul_d = DeviceArray.from_host(self.ctx, mul) if mul is not None else None
+            return self.short_pow_dev(rho, mul_d, False, m).to_host()
+        hs, bits = self._short
+        if rho.shape[0] == 0:
+            return np.zeros((0, self.ct_limbs), dtype=np.uint32)
+        out = self.ctx.powmod(np.tile(self.cipher_limbs([hs]), (rho.shape[0], 1)), rho)
+        if mul is not None:
+            out = self.ctx.mulmod(np.ascontiguousarray(mul), out)
+        if m is not None:
+            out = self.ctx.add_plain(out, m)
+        return out
+
+    def short_fresh_dev(self, count, mul=None, mul_is_pair=False, m=None, want_pair=False, rows=None):
+        """short_pow_dev with freshly drawn exponents, in chunks like raw_encrypt_fresh: the draw (the kernel CSPRNG, host side)
+        and the upload of chunk k+1 overlap the kernel of chunk k.  mul / m: resident rows or None; rows: the indices that get a
+        fresh rho (None: all) — the others get rho = 0, h_s^0 = 1."""
+        hs, bits = self._short
+        el = (bits + 31) // 32
+        st = self._launch_stream()
+        out = DeviceArray(self.ctx, count, self.pair_form() if want_pair else self.ct_limbs)
+        need = None
+        if rows is not None:
+            need = np.zeros(count, dtype=bool)
+            need[rows] = True
+        keep = []
+        lo, chunk = 0, 1 << 15
+        while lo < count:
+            hi = min(count, lo + chunk)
+            rho = random_bits_limbs(bits, hi - lo, el, out=self.scratch("rho", hi - lo, el))
+            if need is not None:
+                rho[~need[lo:hi]] = 0
+            e_d = DeviceArray.from_host(self.ctx, rho)        # synchronous copy: the scratch buffer is free again
+            keep.append(e_d)
+            self._short_launch(e_d, mul.rows_view(lo, hi) if mul is not None else None, mul_is_pair,
+                               m.rows_view(lo, hi) if m is not None else None, out.rows_view(lo, hi), want_pair, st, keep)
             lo, chunk = hi, 1 << 16
         self.ctx.sync(st)
         return out

@@ -18,7 +18,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("PHE_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libphe_hip.so")
 
 OK, EINVAL, EHIP, ENOINVERSE = 0, 1, 2, 3
-ABI_VERSION = 10         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
+ABI_VERSION = 11         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
 
 _lib = None
 
@@ -117,6 +117,11 @@ def lib():
         L.phe_hip_segment_pack_dev.argtypes = [vp, vp, ci, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
         L.phe_hip_slots_pack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
         L.phe_hip_slots_unpack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+        L.phe_hip_fixed_base_set.argtypes = [vp, vp, ci, ci]
+        L.phe_hip_fixed_base_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(sz)]
+        L.phe_hip_fixed_base_clear.argtypes = [vp]
+        L.phe_hip_fixed_base_rows_dev.argtypes = [vp, sz, sz, vp, vp]
+        L.phe_hip_fixed_base_pow_dev.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, sz, vp]
         L.phe_hip_pair_powmod_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp]
         L.phe_hip_pair_multiexp_rows_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, sz, vp]
         _lib = L
@@ -140,6 +145,8 @@ EXPORTED_SYMBOLS = [
     "phe_hip_pair_words", "phe_hip_to_pair_dev", "phe_hip_pair_mul_dev", "phe_hip_from_pair_dev", "phe_hip_pair_reduce_dev",
     "phe_hip_pair_powmod_dev", "phe_hip_pair_multiexp_rows_dev", "phe_hip_segment_reduce_dev",
     "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev", "phe_hip_slots_pack_dev", "phe_hip_slots_unpack_dev",
+    "phe_hip_fixed_base_set", "phe_hip_fixed_base_info", "phe_hip_fixed_base_clear", "phe_hip_fixed_base_rows_dev",
+    "phe_hip_fixed_base_pow_dev",
 ]
 
 
@@ -386,6 +393,30 @@ class Context:
         """out[t] (pair rows) = prod_j rows[t*slots + j] ^ (2^(slot_bits*j)) (include/phe_hip.h phe_hip_segment_pack_dev)"""
         _check(lib().phe_hip_segment_pack_dev(self._h, rows_ptr, 1 if rows_are_pair else 0, n_rows, slots, slot_bits, out_ptr, tasks,
                                               stream))
+
+    # ---- powers of one fixed base by short exponents (include/phe_hip.h phe_hip_fixed_base_*) ----
+    def fixed_base_set(self, hs, exp_bits, window=0):
+        """build the comb table of the residue hs (a Python int) for exponents below 2^exp_bits; window 0: the library's choice"""
+        row = int_to_limbs(int(hs), self.ct_limbs)
+        _check(lib().phe_hip_fixed_base_set(self._h, _ptr(row), int(exp_bits), int(window)))
+
+    def fixed_base_info(self):
+        """{"bits", "window", "positions", "table_bytes"} of the table that is set (all 0: none)"""
+        v = [ctypes.c_int(0) for _ in range(3)]
+        b = ctypes.c_size_t(0)
+        _check(lib().phe_hip_fixed_base_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(b)))
+        return {"bits": v[0].value, "window": v[1].value, "positions": v[2].value, "table_bytes": b.value}
+
+    def fixed_base_clear(self):
+        _check(lib().phe_hip_fixed_base_clear(self._h))
+
+    def fixed_base_rows_dev(self, first, count, out_ptr, stream=0):
+        _check(lib().phe_hip_fixed_base_rows_dev(self._h, first, count, out_ptr, stream))
+
+    def fixed_base_pow_dev(self, e_ptr, exp_limbs, mul_ptr, mul_is_pair, m_ptr, out_ptr, out_is_pair, batch, stream=0):
+        """out[i] = mul[i] * hs^e[i] (* (1 + n*m[i])) (include/phe_hip.h phe_hip_fixed_base_pow_dev)"""
+        _check(lib().phe_hip_fixed_base_pow_dev(self._h, e_ptr, exp_limbs, mul_ptr, 1 if mul_is_pair else 0, m_ptr, out_ptr,
+                                                1 if out_is_pair else 0, batch, stream))
 
     def slots_pack_dev(self, values_ptr, count, slots, slot_bits, m_ptr, rows, stream=0):
         """m_rows[b] = (sum_j values[b*slots + j] * 2^(slot_bits*j)) mod n (include/phe_hip.h phe_hip_slots_pack_dev)"""

@@ -96,6 +96,10 @@ class EncryptedNumber(object):
         if pooled is not None:
             # an obfuscator r^n made ahead of time (PaillierPublicKey.precompute_obfuscators), used once: one product
             self.__ciphertext = eng.to_ints(eng.raw_add([self.__ciphertext % pk.nsquare], pooled.to_host()))[0]
+        elif pk._short is not None:
+            # short-exponent obfuscators (PaillierPublicKey.enable_short_obfuscators): c * h_s^rho for a fresh short rho
+            rows = eng.short_pow(pk._draw_rho(eng, 1), mul=eng.cipher_limbs([self.__ciphertext % pk.nsquare]))
+            self.__ciphertext = eng.to_ints(rows)[0]
         else:
             r = pk.get_random_lt_n()
             self.__ciphertext = eng.to_ints(eng.obfuscate([self.__ciphertext % pk.nsquare], [r]))[0]
@@ -326,12 +330,32 @@ class EncryptedVector(object):
         return [host[i] for i in range(len(self))]
 
     # ---- state -----------------------------------------------------------------------------------------
-    def obfuscate(self, r_values=None):
-        """c_i <- c_i * r_i^n mod n^2 for the rows not yet obfuscated (all rows if r_values is given)."""
+    def obfuscate(self, r_values=None, rho_values=None):
+        """c_i <- c_i * r_i^n mod n^2 for the rows not yet obfuscated (all rows if r_values is given).  With short-exponent
+        obfuscators on (PaillierPublicKey.enable_short_obfuscators) the fresh factor is h_s^rho_i for a short random rho_i, and
+        rho_values gives the exponents explicitly (one per row, all rows): integers in [0, 2^bits) or (rows, ceil(bits / 32))
+        uint32 rows.  A resident vector in the pair form stays in it."""
         pk = self.public_key
         eng = self._eng()
+        if rho_values is not None:
+            rho = pk._rho_limbs(rho_values, len(self), r_values)
+            if len(self) == 0:
+                return self
+            if self._pair and eng.pair_form():
+                self._store = eng.short_pow_dev(rho, mul=self._store, mul_is_pair=True, want_pair=True)
+            elif self.on_device:
+                self._limbs = eng.short_pow_dev(rho, mul=self._limbs)
+            else:
+                self._limbs = eng.short_pow(rho, mul=self._limbs)
+            self._obfuscated[:] = True
+            return self
         rows = np.arange(len(self)) if r_values is not None else np.nonzero(~self._obfuscated)[0]
         if len(rows) == 0:
+            return self
+        if r_values is None and pk._short is not None and not hasattr(eng.ctx, "obfuscate_dev"):
+            # (a backend without resident rows: draw, then the composition of its host calls)
+            self._limbs[rows] = eng.short_pow(pk._draw_rho(eng, len(rows)), mul=np.ascontiguousarray(self._limbs[rows]))
+            self._obfuscated[rows] = True
             return self
         if r_values is None and hasattr(eng.ctx, "obfuscate_dev"):
             # fresh obfuscators as limb arrays straight from the CSPRNG (no Python integer per row)
@@ -347,8 +371,13 @@ class EncryptedVector(object):
                 self._store = eng.pair_mul_dev(self._store, pooled)      # both in pair form: one pair product, stays there
             elif pooled is not None:
                 self._limbs = eng.raw_add_dev(self._limbs, pooled)       # c * r^n with r^n made ahead of time, used once
+            elif self.on_device and self._pair and eng.pair_form() and pk._short is not None:
+                self._store = eng.short_fresh_dev(len(self), mul=self._store, mul_is_pair=True, want_pair=True,
+                                                  rows=None if len(rows) == len(self) else rows)
             elif self.on_device:
                 self._limbs = eng.obfuscate_fresh_dev(self._limbs, None if len(rows) == len(self) else rows)
+            elif pk._short is not None:
+                self._limbs[rows] = eng.short_pow(pk._draw_rho(eng, len(rows)), mul=np.ascontiguousarray(self._limbs[rows]))
             else:
                 from ._engine import random_lt_n_limbs
                 r = random_lt_n_limbs(pk.n, len(rows), eng.n_limbs)

@@ -6,6 +6,7 @@ per-key GPU Engine and batched siblings (`*_batch`) added next to every scalar m
 Key generation and the once-per-key constants (p_inverse, hp, hq) are cold, host-side integer work
 (out of the hot path); everything per-ciphertext runs on the GPU.
 """
+import math
 import random
 import threading
 
@@ -17,6 +18,7 @@ except ImportError:  # pragma: no cover
 import numpy as np
 
 from . import util
+from . import _engine
 from ._engine import Engine, random_lt_n, random_lt_n_limbs
 from .codec import EncodedNumber
 from .sharding import shard_bounds
@@ -78,6 +80,7 @@ class PaillierPublicKey(object):
         self._engine_lock = threading.Lock()
         self._fleet = None
         self._fleet_factory = None               # device -> Engine for the further devices of a fleet (a key pair installs its own)
+        self._short = None                       # (h_s, bits) while short-exponent obfuscators are on (enable_short_obfuscators)
 
     # one GPU context per key, created on first use (a private key shares its context with its public key); the creation
     # is guarded so that two threads never build two contexts — and two obfuscator pools — for one key
@@ -88,6 +91,14 @@ class PaillierPublicKey(object):
                 if self._engine is None:
                     self._engine = Engine(self.n)
                 eng = self._engine
+        return self._short_sync(eng)
+
+    def _short_sync(self, eng):
+        """the engine, told the key's short-obfuscator setting if it does not have it yet (every engine of the key — of a fleet,
+        or one that took over from another — builds its own table from it, on first use)"""
+        want = self._short
+        if eng.short_base() != want:
+            eng.set_short_base(*(want or (None, 0)))
         return eng
 
     def _get_fleet(self):
@@ -118,14 +129,14 @@ class PaillierPublicKey(object):
         if fl is not None:
             eng = fl.engine_of(ctx)
             if eng is not None:
-                return eng
+                return self._short_sync(eng)
         device = getattr(ctx, "device", None)
         if device is None or device == primary.device:
             return primary          # another context of the primary's GPU (e.g. the public engine a key pair's engine replaced)
         if fl is not None:
             eng = fl.engine_on(device)
             if eng is not None:
-                return eng
+                return self._short_sync(eng)
         # never launch one device's kernels on another device's pointers (nothing here enables peer access)
         raise RuntimeError("resident rows live on device %r, which no engine of this key serves (engines on %r): move them "
                            "through the host (vector.to_host())" % (device, [primary.device] + (fl.devices[1:] if fl else [])))
@@ -180,7 +191,12 @@ class PaillierPublicKey(object):
                     number = EncryptedNumber(self, eng.to_ints(limbs.to_host())[0], encoding.exponent)
                     number._EncryptedNumber__is_obfuscated = True
                     return number
-            c = self.raw_encrypt(encoding.encoding, self.get_random_lt_n())
+            if self._short is not None:
+                if not isinstance(encoding.encoding, int):
+                    raise TypeError('Expected int type plaintext but got: %s' % type(encoding.encoding))
+                c = eng.to_ints(eng.short_pow(self._draw_rho(eng, 1), m=[encoding.encoding]))[0]
+            else:
+                c = self.raw_encrypt(encoding.encoding, self.get_random_lt_n())
             number = EncryptedNumber(self, c, encoding.exponent)
             number._EncryptedNumber__is_obfuscated = True
             return number
@@ -202,7 +218,8 @@ class PaillierPublicKey(object):
             # the devices a batch of `count` rows fans out to fill THEIR pools with the shares that batch will take from them
             # (a pool is never shared across devices; a batch too small to fan out, and every scalar call, is served by the
             # primary engine alone — so a small `count` goes there whole instead of being spread where nothing would use it)
-            futures = [fl._pool.submit(fl.engine(k).fill_obfuscator_pool, hi - lo) for k, (lo, hi) in enumerate(bounds)]
+            futures = [fl._pool.submit(self._short_sync(fl.engine(k)).fill_obfuscator_pool, hi - lo)
+                       for k, (lo, hi) in enumerate(bounds)]
             for f in futures:
                 f.result()
             return self.obfuscators_available()
@@ -221,6 +238,107 @@ class PaillierPublicKey(object):
         for eng in (fl.made() if fl is not None else [self._get_engine()]):
             eng.clear_obfuscator_pool()
 
+    # ---- short-exponent obfuscators ---------------------------------------------------------------------
+    def enable_short_obfuscators(self, bits=None, x=None, hs=None):
+        """Draw every fresh obfuscator as h_s^rho mod n^2 for a short random exponent rho in [0, 2^bits) instead of r^n for a
+        fresh r in [1, n) — the variant of Damgard, Jurik and Nielsen that production Paillier stacks offer.  With a
+        unit x, h = -x^2 mod n and h_s = h^n mod n^2, the obfuscator h_s^rho = (h^rho)^n is an n-th power, so decryption is
+        unchanged, and c = (1 + n m) * h_s^rho is bit for bit raw_encrypt(m, r_value=pow(h, rho, n)).  The base is the same for
+        every ciphertext: the GPU multiplies ceil(bits / w) entries of a table of powers of h_s and squares nothing
+        (csrc/fixed_base.h).  Returns h_s.
+        bits: the length of rho, default n.bit_length() // 2 (outside [1, n.bit_length()]: ValueError; not an integer:
+        TypeError).  x: the unit h is made of, default a CSPRNG draw from [1, n) with gcd(x, n) = 1 (a given x that shares a
+        factor with n, or lies outside [1, n): ValueError).  hs: a ready h_s handed out by the key owner, instead of x (both:
+        ValueError); it must satisfy 1 < hs < n^2 and be coprime to n.
+        AN h_s THAT IS NOT AN n-TH POWER CORRUPTS EVERY PLAINTEXT ENCRYPTED WITH IT, AND NOTHING HERE CAN DETECT THAT: a public
+        key cannot tell n-th powers from other residues — that is the assumption Paillier encryption rests on.  Take hs only
+        from whoever made the key.
+        What the scheme assumes beyond the reference's: that h_s^rho for short rho cannot be told from a random n-th power
+        (short exponents in the subgroup generated by h).  It applies from now on to encrypt, encrypt_batch, encrypt_packed,
+        encrypt_batch_sharded, precompute_obfuscators and obfuscate(); explicit r_values keep meaning the reference's r, and
+        obfuscators already in the pool stay valid and are used up.  The setting is not part of ==, hash() or pickling."""
+        nbits = self.n.bit_length()
+        if bits is None:
+            bits = nbits // 2
+        if isinstance(bits, (bool, np.bool_)) or not isinstance(bits, (int, np.integer)):
+            raise TypeError("bits must be an integer")
+        bits = int(bits)
+        if not 1 <= bits <= nbits:
+            raise ValueError("bits must lie in [1, %d]" % nbits)
+        if x is not None and hs is not None:
+            raise ValueError("give x or hs, not both")
+        if hs is None:
+            if x is None:
+                rng = random.SystemRandom()
+                x = rng.randrange(1, self.n)
+                while math.gcd(x, self.n) != 1:
+                    x = rng.randrange(1, self.n)
+            else:
+                if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                    raise TypeError("x must be an integer")
+                x = int(x)
+                if not 1 <= x < self.n or math.gcd(x, self.n) != 1:
+                    raise ValueError("x must lie in [1, n) and share no factor with n")
+            hs = pow((-x * x) % self.n, self.n, self.nsquare)
+        else:
+            if isinstance(hs, (bool, np.bool_)) or not isinstance(hs, (int, np.integer)):
+                raise TypeError("hs must be an integer")
+            hs = int(hs)
+        if not 1 < hs < self.nsquare or math.gcd(hs, self.n) != 1:
+            raise ValueError("h_s must lie in (1, n^2) and share no factor with n")
+        self._short = (hs, bits)
+        return hs
+
+    def disable_short_obfuscators(self):
+        """fresh obfuscators are r^n for r in [1, n) again (the reference's); the tables of powers of h_s are dropped"""
+        self._short = None
+        fl = self._fleet
+        for eng in (fl.made() if fl is not None else [self._engine] if self._engine is not None else []):
+            self._short_sync(eng)
+
+    @property
+    def short_obfuscator_base(self):
+        """h_s while short-exponent obfuscators are on, else None"""
+        return self._short[0] if self._short is not None else None
+
+    @property
+    def short_obfuscator_bits(self):
+        """the length of the exponents rho while short-exponent obfuscators are on, else None"""
+        return self._short[1] if self._short is not None else None
+
+    def _draw_rho(self, eng, count):
+        """`count` fresh exponents as limb rows"""
+        bits = self._short[1]
+        return _engine.random_bits_limbs(bits, count, (bits + 31) // 32)
+
+    def _rho_limbs(self, rho_values, count, r_values=None):
+        """the explicit exponents of a `rho_values=` argument as (count, ceil(bits / 32)) limb rows, checked"""
+        from . import _native
+        if r_values is not None:
+            raise ValueError("give r_values or rho_values, not both")
+        if self._short is None:
+            raise ValueError("rho_values need short obfuscators: call enable_short_obfuscators() first")
+        bits = self._short[1]
+        el = (bits + 31) // 32
+        if isinstance(rho_values, np.ndarray) and rho_values.ndim == 2:
+            if rho_values.dtype != np.uint32 or rho_values.shape != (count, el):
+                raise ValueError("rho_values as an array must be (%d, %d) uint32 rows, not %s %s"
+                                 % (count, el, rho_values.shape, rho_values.dtype))
+            if bits < 32 * el:
+                bad = np.flatnonzero(rho_values[:, el - 1] >> np.uint32(bits - 32 * (el - 1)))
+                if len(bad):
+                    raise ValueError("rho_values[%d] lies outside [0, 2^%d)" % (bad[0], bits))
+            return np.ascontiguousarray(rho_values)
+        vals = [int(v) if isinstance(v, np.integer) else v for v in rho_values]
+        if len(vals) != count:
+            raise ValueError("%d rho_values for %d rows" % (len(vals), count))
+        for i, v in enumerate(vals):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError("rho_values[%d] is not an integer" % i)
+            if not 0 <= v < 1 << bits:
+                raise ValueError("rho_values[%d] lies outside [0, 2^%d)" % (i, bits))
+        return _native.ints_to_limbs(vals, el)
+
     # ---- batched API ------------------------------------------------------------------------------
     def raw_encrypt_batch(self, plaintexts, r_values=None):
         """List of ints -> list of int ciphertexts; r_values=None draws fresh obfuscators."""
@@ -233,13 +351,15 @@ class PaillierPublicKey(object):
         eng = self._get_engine()
         return eng.to_ints(eng.raw_encrypt(plaintexts, list(r_values)))
 
-    def encrypt_batch(self, values, precision=None, r_values=None, device=False):
+    def encrypt_batch(self, values, precision=None, r_values=None, device=False, rho_values=None):
         """Encode + encrypt a whole sequence / numpy array -> EncryptedVector (one kernel launch).
         device=True keeps the ciphertexts resident in HBM for later homomorphic operations.
-        float64 / integer numpy arrays are encoded and drawn without a Python integer per element."""
+        float64 / integer numpy arrays are encoded and drawn without a Python integer per element.
+        rho_values (with enable_short_obfuscators): the exponents of the obfuscators h_s^rho given explicitly, as integers in
+        [0, 2^bits) or (count, ceil(bits / 32)) uint32 rows — row i is raw_encrypt(m_i, r_value=pow(h, rho_i, n))."""
         from .ciphertext import EncryptedVector
         eng = self._get_engine()
-        fresh = r_values is None
+        fresh = r_values is None and rho_values is None
         signed = EncodedNumber.encode_signed(values, precision) if eng.n_limbs >= 4 else None
         if signed is not None:
             mag, neg, exps = signed
@@ -248,12 +368,19 @@ class PaillierPublicKey(object):
             m, exps = EncodedNumber.encode_many(self, values, precision)
         count = len(exps)
         limbs = None
+        if rho_values is not None:
+            rho = self._rho_limbs(rho_values, count, r_values)
+            limbs = eng.short_pow_dev(rho, m=m) if device else eng.short_pow(rho, m=m)
+            return EncryptedVector(self, limbs, exps, obfuscated=False)
         fl = self._get_fleet() if (not device and isinstance(m, np.ndarray)) else None
         if fl is not None and len(fl.shards(count)) > 1:
             # single-process fan-out (phe/fleet.py): contiguous shards, one device each, results into ONE host array
             if fresh:
                 def shard(e, lo, hi):
+                    self._short_sync(e)
                     if not hasattr(e.ctx, "encrypt_dev"):           # (a backend without resident rows: draw, then one call)
+                        if self._short is not None:
+                            return e.short_pow(self._draw_rho(e, hi - lo), m=m[lo:hi])
                         return e.raw_encrypt(m[lo:hi], random_lt_n_limbs(self.n, hi - lo, e.n_limbs))
                     got = e.encrypt_from_obfuscators(m[lo:hi])      # the device's own pool first (each obfuscator used once)
                     return got.to_host() if got is not None else e.raw_encrypt_fresh(m[lo:hi], False)
@@ -272,6 +399,9 @@ class PaillierPublicKey(object):
                 limbs = limbs.to_host()
         elif fresh and isinstance(m, np.ndarray) and hasattr(eng.ctx, "encrypt_dev"):
             limbs = eng.raw_encrypt_fresh(m, device)
+        elif fresh and self._short is not None:
+            rho = self._draw_rho(eng, count)
+            limbs = eng.short_pow_dev(rho, m=m) if device else eng.short_pow(rho, m=m)
         else:
             r = random_lt_n_limbs(self.n, count, eng.n_limbs) if fresh else list(r_values)
             limbs = eng.raw_encrypt_dev(m, r) if device else eng.raw_encrypt(m, r)
@@ -359,7 +489,7 @@ class PaillierPublicKey(object):
             ms = [sum(x << (B * j) for j, x in enumerate(xs[b * S:(b + 1) * S])) % n for b in range(rows)]
         return _native.ints_to_limbs(ms, n_limbs)
 
-    def encrypt_packed(self, values, slots, slot_bits, precision=None, r_values=None, device=False):
+    def encrypt_packed(self, values, slots, slot_bits, precision=None, r_values=None, device=False, rho_values=None):
         """Encode, PACK and encrypt -> EncryptedVector of ceil(len(values) / slots) rows: row b encrypts
         V_b = x[b*S] + x[b*S + 1] * 2^B + x[b*S + 2] * 2^(2B) + ... (S = slots, B = slot_bits) for the signed mantissas x of the
         values — what EncryptedVector.pack(S, B) makes of encrypt_batch(values), for one encryption per S values instead of S
@@ -372,8 +502,8 @@ class PaillierPublicKey(object):
         element (an exact power-of-two scaling, then rounding half to even).  A mantissa outside [-2^(B-1), 2^(B-1)) raises
         ValueError with its index.  slots / slot_bits are checked as EncryptedVector.pack checks them: not an integer —
         TypeError, below 1 — ValueError, slots * slot_bits > max_int.bit_length() - 1 — ValueError.
-        Row b is bit for bit raw_encrypt(V_b mod n, r_b); r_values, the obfuscator pool and device=True behave as in
-        encrypt_batch.  The plaintext rows are formed on the GPU (Engine.slots_pack_dev: shifts and one reduction mod n, a
+        Row b is bit for bit raw_encrypt(V_b mod n, r_b); r_values, rho_values (one per packed ROW), the obfuscator pool and
+        device=True behave as in encrypt_batch.  The plaintext rows are formed on the GPU (Engine.slots_pack_dev: shifts and one reduction mod n, a
         memory-bound kernel) and stay there; without that kernel, or for slot_bits > 64, they are formed on the host: same bits.
         WHAT CANNOT BE CHECKED UNDER ENCRYPTION (EncryptedVector.pack): a slot whose true value, after every later addition or
         scaling of packed vectors, leaves [-2^(B-1), 2^(B-1)) spills into its neighbour, silently.  Choosing slot_bits with
@@ -403,14 +533,24 @@ class PaillierPublicKey(object):
         eng = self._get_engine()
         rows = -(-count // S)
         exps = np.full(rows, exponent, dtype=np.int64)
-        fresh = r_values is None
+        fresh = r_values is None and rho_values is None
+        rho = self._rho_limbs(rho_values, rows, r_values) if rho_values is not None else None
         if rows == 0:
             empty = DeviceArray(eng.ctx, 0, eng.ct_limbs) if device else np.zeros((0, eng.ct_limbs), dtype=np.uint32)
             return EncryptedVector(self, empty, exps, obfuscated=fresh)
         resident = isinstance(mant, np.ndarray) and B <= 64 and eng.has_slot_codec()
         m = eng.slots_pack_dev(mant, S, B) if resident else self._pack_plain_host(mant, S, B)
         limbs = None
-        if fresh and hasattr(eng.ctx, "encrypt_dev"):
+        if rho is not None or (fresh and self._short is not None and not hasattr(eng.ctx, "encrypt_dev")):
+            if rho is None:
+                rho = self._draw_rho(eng, rows)
+            if device or resident:
+                limbs = eng.short_pow_dev(rho, m=m)
+                if not device:
+                    limbs = limbs.to_host()
+            else:
+                limbs = eng.short_pow(rho, m=m)
+        elif fresh and hasattr(eng.ctx, "encrypt_dev"):
             limbs = eng.encrypt_from_obfuscators(m)                 # the pool made by precompute_obfuscators (each used once)
             if limbs is None and rows <= SCALAR_POOL_REFILL // 4:
                 eng.fill_obfuscator_pool(SCALAR_POOL_REFILL)
@@ -453,6 +593,7 @@ class PaillierPublicKey(object):
         exps = np.asarray(exps, dtype=np.int64)
 
         def shard(e, lo, hi):
+            self._short_sync(e)
             got = e.encrypt_from_obfuscators(m[lo:hi])
             return got if got is not None else e.raw_encrypt_fresh(m[lo:hi], True)
         bounds = fl.shards(len(exps), min_rows=1)
