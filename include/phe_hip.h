@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 11
+#define PHE_HIP_ABI_VERSION 12
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -336,6 +336,15 @@ int phe_hip_fixed_base_clear(phe_hip_ctx* ctx);
 int phe_hip_fixed_base_rows_dev(phe_hip_ctx* ctx, size_t first, size_t count, uint32_t* out_pair, void* stream);
 int phe_hip_fixed_base_pow_dev(phe_hip_ctx* ctx, const uint32_t* e, int exp_limbs, const uint32_t* mul, int mul_is_pair,
                                const uint32_t* m, uint32_t* out, int out_is_pair, size_t batch, void* stream);
+/* Rows of random exponent words drawn on the device (csrc/chacha_rows.h): the ChaCha20 keystream (RFC 8439, 20 rounds) of `key`
+ * under `nonce`, from block `counter0` on, as out (rows, limbs) 32-bit words on the device.  A row takes B = ceil(limbs / 16)
+ * blocks of its own: word w of row i is word w % 16 of block counter0 + i*B + w / 16, and what a row leaves of its last block is
+ * discarded.  Bits at or above `bits` in limb (bits - 1) / 32 are cleared, limbs above it are zero.  `key` (8 words) and `nonce`
+ * (3 words) are HOST pointers, read before the call returns; they travel in the kernel's arguments and no device allocation holds
+ * them.  EINVAL: a null key, nonce or out, bits < 1 or bits > 32*limbs, counter0 + rows*B > 2^32 (the counter never wraps inside
+ * one call).  rows == 0 is OK and launches nothing. */
+int phe_hip_chacha20_rows_dev(phe_hip_ctx* ctx, const uint32_t key[8], const uint32_t nonce[3], uint32_t counter0, int bits,
+                              int limbs, uint32_t* out, size_t rows, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

@@ -33,6 +33,7 @@
 #include "segment_core.h"
 #include "slot_codec.h"
 #include "fixed_base.h"
+#include "chacha_rows.h"
 #include "mul_io.h"
 #include "mul_table.h"
 #include "decrypt_tail.h"
@@ -135,6 +136,9 @@ int launch_slots_unpack(int G, int K, int blocks, hipStream_t st, const SlotUnpa
 namespace fb {  // kernels_fb.hip
 int launch_fixed_base_pow(int G, int L, int blocks, hipStream_t st, const FixedBaseArgs& A, bool mul_is_residue, bool exit);
 }  // namespace fb
+namespace rng {  // kernels_rng.hip
+int launch_chacha_rows(int blocks, hipStream_t st, const ChaChaRowsArgs& A);
+}  // namespace rng
 }  // namespace phe
 
 namespace phe {
@@ -2350,6 +2354,39 @@ int phe_hip_fixed_base_pow_dev(phe_hip_ctx* ctx, const uint32_t* e, int exp_limb
     const int blocks = grid_blocks(ctx, batch, sp.G, 2);
     if (phe::fb::launch_fixed_base_pow(sp.G, sp.L, blocks, (hipStream_t)stream, A, mul && !mul_is_pair, !out_is_pair) < 0)
         return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// out (rows, limbs) = the ChaCha20 keystream of (key, nonce) from block counter0 on, every row cut to `bits` bits
+// (chacha_rows.h chacha_rows_body): the random exponents of the short obfuscators, drawn where the comb kernel reads them.  Key
+// and nonce are copied into the kernel's arguments; this function's own copy is overwritten before it returns, and no message
+// of fail() carries a word of them.
+int phe_hip_chacha20_rows_dev(phe_hip_ctx* ctx, const uint32_t key[8], const uint32_t nonce[3], uint32_t counter0, int bits,
+                              int limbs, uint32_t* out, size_t rows, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (!key || !nonce || !out) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (limbs < 1 || bits < 1 || (int64_t)bits > 32 * (int64_t)limbs) return fail(PHE_HIP_EINVAL, "bits must be in 1 .. 32 * limbs");
+    const uint64_t B = ((uint64_t)limbs + 15) / 16;
+    if ((uint64_t)rows > (((uint64_t)1 << 32) - counter0) / B)
+        return fail(PHE_HIP_EINVAL, "counter0 + rows * ceil(limbs / 16) exceeds 2^32: the block counter would wrap");
+    if (rows == 0) return PHE_HIP_OK;
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    ChaChaRowsArgs A;
+    memcpy(A.key, key, sizeof A.key);
+    memcpy(A.nonce, nonce, sizeof A.nonce);
+    A.counter0 = counter0;
+    A.bits = bits;
+    A.limbs = limbs;
+    A.blocks_per_row = (int)B;
+    A.out = out;
+    A.rows = rows;
+    // one lane per block: enough workgroups to fill the device eight times over, the rest grid-strided
+    const uint64_t want = ((uint64_t)rows * B + kBlock - 1) / kBlock;
+    const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->n_cus * 8));
+    phe::rng::launch_chacha_rows(blocks, (hipStream_t)stream, A);  // (the arguments are copied by the launch call)
+    for (volatile uint32_t* w = A.key; w != A.key + 8; ++w) *w = 0;
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;
 }

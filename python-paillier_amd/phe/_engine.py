@@ -17,7 +17,7 @@ import threading
 
 import numpy as np
 
-from . import _native
+from . import _chacha, _native
 from ._device import DeviceArray
 
 
@@ -123,6 +123,41 @@ def random_bits_limbs(bits, count, limbs, out=None):
         out[:, top_limb] &= np.uint32((1 << top_bits) - 1)
     if top_limb + 1 < limbs:
         out[:, top_limb + 1:] = 0
+    return out
+
+
+def fresh_seed():
+    """32 bytes from the kernel CSPRNG in a bytearray: the ChaCha20 key of ONE launch of the device draw (Engine.random_bits_dev,
+    csrc/chacha_rows.h).  The only source of seeds — no clock, no pid, no `random`, no environment override — and the caller
+    overwrites the bytearray with zeros as soon as the launch call has returned: a seed is as sensitive as the exponents it
+    expands to."""
+    seed = bytearray(32)
+    _urandom_into(seed)
+    return seed
+
+
+_SEED_NONCE = (0, 0, 0)      # a seed keys one launch and is never used again: the nonce and the first counter are 0
+
+
+def _seeded_parts(count, limbs):
+    """[lo, hi) row ranges of a seeded draw: one launch takes at most 2^32 keystream blocks (the block counter never wraps)"""
+    step = (1 << 32) // _chacha.blocks_per_row(limbs)
+    return [(lo, min(count, lo + step)) for lo in range(0, count, step)]
+
+
+def seeded_bits_limbs(bits, count, limbs):
+    """random_bits_limbs by the host expander (phe/_chacha.py) under fresh seeds: the draw of the short exponents while the
+    key's device_rng setting is on, where rows are wanted on the host"""
+    bits, limbs = int(bits), int(limbs)
+    if bits < 1 or bits > 32 * limbs:
+        raise ValueError("bits must lie in [1, %d]" % (32 * limbs))
+    out = np.empty((count, limbs), dtype=np.uint32)
+    for lo, hi in _seeded_parts(count, limbs):
+        seed = fresh_seed()
+        try:
+            out[lo:hi] = _chacha.chacha20_rows(seed, _SEED_NONCE, 0, bits, limbs, hi - lo)
+        finally:
+            seed[:] = bytes(len(seed))
     return out
 
 
@@ -702,18 +737,24 @@ class Engine:
         st = self._launch_stream()
         short = self.short_base()
         el = (short[1] + 31) // 32 if short else 0
+        seeded = bool(short) and self.short_device_rng()  # rho drawn where the comb kernel reads it: no host buffer, no upload
         out = DeviceArray(self.ctx, count, self.ct_limbs)
         host = None if device else np.empty((count, self.ct_limbs), dtype=np.uint32)
         keep = []                                         # operand buffers stay alive until the final sync
         lo, chunk, prev = 0, 1 << 15, None                # chunks are multiples of the groups in flight (32768 at 2048 bits)
         while lo < count:
             hi = min(count, lo + chunk)
-            if short:                                     # short-exponent obfuscators: rho instead of r, h_s^rho instead of r^n
+            if seeded:
+                r = None
+            elif short:                                   # short-exponent obfuscators: rho instead of r, h_s^rho instead of r^n
                 r = random_bits_limbs(short[1], hi - lo, el, out=self.scratch("rho", hi - lo, el))
             else:
                 r = random_lt_n_limbs(self.n, hi - lo, self.n_limbs, out=self.scratch("r", hi - lo, self.n_limbs))
             m_d = m.rows_view(lo, hi) if resident else DeviceArray.from_host(self.ctx, m[lo:hi])
-            r_d = DeviceArray.from_host(self.ctx, r)      # synchronous copy: the scratch buffer is free again
+            if seeded:
+                r_d = self.random_bits_dev(short[1], hi - lo, el, st)
+            else:
+                r_d = DeviceArray.from_host(self.ctx, r)  # synchronous copy: the scratch buffer is free again
             keep += [m_d, r_d]
             if host is not None and st:
                 self.ctx.sync(st)                         # the previous chunk is complete (its successor starts right away)
@@ -1134,6 +1175,38 @@ class Engine:
             raise ValueError("bits must lie in [1, %d]" % self.n.bit_length())
         self._short = (hs, bits)
 
+    def short_device_rng(self):
+        """True while the short exponents of whole batches are ChaCha20 output under per-launch seeds (set_short_device_rng)"""
+        return bool(self.__dict__.get("_short_rng"))
+
+    def set_short_device_rng(self, on):
+        """the key's device_rng setting (PaillierPublicKey.enable_short_obfuscators); nothing is built or kept for it"""
+        self._short_rng = bool(on)
+
+    def random_bits_dev(self, bits, count, limbs, st=0):
+        """`count` random integers in [0, 2^bits) as resident (count, limbs) rows, queued on stream `st`: the ChaCha20 keystream
+        (RFC 8439) of a fresh 32-byte seed from the kernel CSPRNG (fresh_seed), nonce 0, from block 0 on, expanded by the kernel
+        of csrc/chacha_rows.h — or, on a backend without it, by the host expander (phe/_chacha.py, same words) and uploaded.
+        One seed per launch, handed to the kernel in its arguments and overwritten here as soon as the launch call has returned;
+        nothing is kept between calls, so a forked process, another thread and every engine of a fleet draw seeds of their own.
+        A draw of more than 2^32 blocks is cut, each part under its own seed."""
+        bits, limbs = int(bits), int(limbs)
+        if bits < 1 or bits > 32 * limbs:
+            raise ValueError("bits must lie in [1, %d]" % (32 * limbs))
+        out = DeviceArray(self.ctx, count, limbs)
+        kernel = hasattr(self.ctx, "chacha20_rows_dev")
+        for lo, hi in _seeded_parts(count, limbs):
+            part = out.rows_view(lo, hi)
+            seed = fresh_seed()
+            try:
+                if kernel:
+                    self.ctx.chacha20_rows_dev(seed, _SEED_NONCE, 0, bits, limbs, part.ptr, hi - lo, st)
+                else:
+                    self.ctx.h2d(part.ptr, _chacha.chacha20_rows(seed, _SEED_NONCE, 0, bits, limbs, hi - lo))
+            finally:
+                seed[:] = bytes(len(seed))
+        return out
+
     def has_fixed_base(self):
         """True when h_s^rho has its kernel: a base is set, the pair form is offered and the backend has the entry points"""
         return self.short_base() is not None and bool(self.pair_form()) and hasattr(self.ctx, "fixed_base_pow_dev")
@@ -1235,7 +1308,8 @@ class Engine:
     def short_fresh_dev(self, count, mul=None, mul_is_pair=False, m=None, want_pair=False, rows=None):
         """short_pow_dev with freshly drawn exponents, in chunks like raw_encrypt_fresh: the draw (the kernel CSPRNG, host side)
         and the upload of chunk k+1 overlap the kernel of chunk k.  mul / m: resident rows or None; rows: the indices that get a
-        fresh rho (None: all) — the others get rho = 0, h_s^0 = 1."""
+        fresh rho (None: all) — the others get rho = 0, h_s^0 = 1.  With the key's device_rng setting and rows None, every
+        chunk's exponents are drawn on the device under a seed of its own (random_bits_dev): no host buffer, no upload."""
         hs, bits = self._short
         el = (bits + 31) // 32
         st = self._launch_stream()
@@ -1248,10 +1322,13 @@ class Engine:
         lo, chunk = 0, 1 << 15
         while lo < count:
             hi = min(count, lo + chunk)
-            rho = random_bits_limbs(bits, hi - lo, el, out=self.scratch("rho", hi - lo, el))
-            if need is not None:
-                rho[~need[lo:hi]] = 0
-            e_d = DeviceArray.from_host(self.ctx, rho)        # synchronous copy: the scratch buffer is free again
+            if need is None and self.short_device_rng():
+                e_d = self.random_bits_dev(bits, hi - lo, el, st)
+            else:                                             # (a part of the vector: the rows that get rho = 0 are picked on the host)
+                rho = random_bits_limbs(bits, hi - lo, el, out=self.scratch("rho", hi - lo, el))
+                if need is not None:
+                    rho[~need[lo:hi]] = 0
+                e_d = DeviceArray.from_host(self.ctx, rho)    # synchronous copy: the scratch buffer is free again
             keep.append(e_d)
             self._short_launch(e_d, mul.rows_view(lo, hi) if mul is not None else None, mul_is_pair,
                                m.rows_view(lo, hi) if m is not None else None, out.rows_view(lo, hi), want_pair, st, keep)

@@ -18,7 +18,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("PHE_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libphe_hip.so")
 
 OK, EINVAL, EHIP, ENOINVERSE = 0, 1, 2, 3
-ABI_VERSION = 11         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
+ABI_VERSION = 12         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
 
 _lib = None
 
@@ -122,6 +122,7 @@ def lib():
         L.phe_hip_fixed_base_clear.argtypes = [vp]
         L.phe_hip_fixed_base_rows_dev.argtypes = [vp, sz, sz, vp, vp]
         L.phe_hip_fixed_base_pow_dev.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, sz, vp]
+        L.phe_hip_chacha20_rows_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ci, ci, vp, sz, vp]
         L.phe_hip_pair_powmod_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp]
         L.phe_hip_pair_multiexp_rows_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, sz, vp]
         _lib = L
@@ -146,7 +147,7 @@ EXPORTED_SYMBOLS = [
     "phe_hip_pair_powmod_dev", "phe_hip_pair_multiexp_rows_dev", "phe_hip_segment_reduce_dev",
     "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev", "phe_hip_slots_pack_dev", "phe_hip_slots_unpack_dev",
     "phe_hip_fixed_base_set", "phe_hip_fixed_base_info", "phe_hip_fixed_base_clear", "phe_hip_fixed_base_rows_dev",
-    "phe_hip_fixed_base_pow_dev",
+    "phe_hip_fixed_base_pow_dev", "phe_hip_chacha20_rows_dev",
 ]
 
 
@@ -417,6 +418,25 @@ class Context:
         """out[i] = mul[i] * hs^e[i] (* (1 + n*m[i])) (include/phe_hip.h phe_hip_fixed_base_pow_dev)"""
         _check(lib().phe_hip_fixed_base_pow_dev(self._h, e_ptr, exp_limbs, mul_ptr, 1 if mul_is_pair else 0, m_ptr, out_ptr,
                                                 1 if out_is_pair else 0, batch, stream))
+
+    def chacha20_rows_dev(self, key, nonce, counter0, bits, limbs, out_ptr, rows, stream=0):
+        """out (rows, limbs) = the ChaCha20 keystream of key (32 bytes or 8 words) / nonce (12 bytes or 3 words) from block
+        counter0 on, every row cut to `bits` bits (include/phe_hip.h phe_hip_chacha20_rows_dev).  The words are handed over in
+        ctypes arrays of this call's own, zeroed before it returns; nothing but the status reaches an error message."""
+        def words(src, count):      # None stays a null pointer: the library refuses it
+            if src is None:
+                return None
+            T = ctypes.c_uint32 * count
+            return T.from_buffer_copy(src) if isinstance(src, (bytes, bytearray)) else T(*[int(w) for w in src])
+        if not 0 <= int(counter0) < 1 << 32:
+            raise ValueError("counter0 must fit 32 bits")
+        k, v = words(key, 8), words(nonce, 3)
+        try:
+            rc = lib().phe_hip_chacha20_rows_dev(self._h, k, v, int(counter0), int(bits), int(limbs), out_ptr, rows, stream)
+        finally:
+            if k is not None:
+                ctypes.memset(k, 0, ctypes.sizeof(k))
+        _check(rc)
 
     def slots_pack_dev(self, values_ptr, count, slots, slot_bits, m_ptr, rows, stream=0):
         """m_rows[b] = (sum_j values[b*slots + j] * 2^(slot_bits*j)) mod n (include/phe_hip.h phe_hip_slots_pack_dev)"""

@@ -81,6 +81,7 @@ class PaillierPublicKey(object):
         self._fleet = None
         self._fleet_factory = None               # device -> Engine for the further devices of a fleet (a key pair installs its own)
         self._short = None                       # (h_s, bits) while short-exponent obfuscators are on (enable_short_obfuscators)
+        self._short_rng = False                  # its device_rng flag: rho of whole batches from per-launch ChaCha20 seeds
 
     # one GPU context per key, created on first use (a private key shares its context with its public key); the creation
     # is guarded so that two threads never build two contexts — and two obfuscator pools — for one key
@@ -99,6 +100,8 @@ class PaillierPublicKey(object):
         want = self._short
         if eng.short_base() != want:
             eng.set_short_base(*(want or (None, 0)))
+        if eng.short_device_rng() != self._short_rng:
+            eng.set_short_device_rng(self._short_rng)
         return eng
 
     def _get_fleet(self):
@@ -239,7 +242,7 @@ class PaillierPublicKey(object):
             eng.clear_obfuscator_pool()
 
     # ---- short-exponent obfuscators ---------------------------------------------------------------------
-    def enable_short_obfuscators(self, bits=None, x=None, hs=None):
+    def enable_short_obfuscators(self, bits=None, x=None, hs=None, device_rng=False):
         """Draw every fresh obfuscator as h_s^rho mod n^2 for a short random exponent rho in [0, 2^bits) instead of r^n for a
         fresh r in [1, n) — the variant of Damgard, Jurik and Nielsen that production Paillier stacks offer.  With a
         unit x, h = -x^2 mod n and h_s = h^n mod n^2, the obfuscator h_s^rho = (h^rho)^n is an n-th power, so decryption is
@@ -256,7 +259,15 @@ class PaillierPublicKey(object):
         What the scheme assumes beyond the reference's: that h_s^rho for short rho cannot be told from a random n-th power
         (short exponents in the subgroup generated by h).  It applies from now on to encrypt, encrypt_batch, encrypt_packed,
         encrypt_batch_sharded, precompute_obfuscators and obfuscate(); explicit r_values keep meaning the reference's r, and
-        obfuscators already in the pool stay valid and are used up.  The setting is not part of ==, hash() or pickling."""
+        obfuscators already in the pool stay valid and are used up.  The setting is not part of ==, hash() or pickling.
+        device_rng (off by default): where the exponents of a whole batch come from.  Off: every rho is read from the kernel
+        CSPRNG (/dev/urandom) by the host and uploaded.  On: for encrypt_batch, encrypt_packed, encrypt_batch_sharded,
+        precompute_obfuscators and whole-vector obfuscate(), the host reads only a 32-byte seed per launch from the kernel CSPRNG
+        and the rho are the ChaCha20 keystream (RFC 8439, 20 rounds) under that 256-bit key, expanded on the GPU where the comb
+        kernel reads them — the construction /dev/urandom itself uses, one level down.  A seed is used for one launch, travels
+        in the kernel's arguments, is overwritten on the host when the launch call returns and is never cached, logged or put in
+        an error message; it is as sensitive as the exponents it expands to.  Scalar calls and obfuscate(rows=...) keep the host
+        draw; rho_values= and r_values= are unaffected."""
         nbits = self.n.bit_length()
         if bits is None:
             bits = nbits // 2
@@ -287,11 +298,13 @@ class PaillierPublicKey(object):
         if not 1 < hs < self.nsquare or math.gcd(hs, self.n) != 1:
             raise ValueError("h_s must lie in (1, n^2) and share no factor with n")
         self._short = (hs, bits)
+        self._short_rng = bool(device_rng)
         return hs
 
     def disable_short_obfuscators(self):
         """fresh obfuscators are r^n for r in [1, n) again (the reference's); the tables of powers of h_s are dropped"""
         self._short = None
+        self._short_rng = False
         fl = self._fleet
         for eng in (fl.made() if fl is not None else [self._engine] if self._engine is not None else []):
             self._short_sync(eng)
@@ -306,9 +319,18 @@ class PaillierPublicKey(object):
         """the length of the exponents rho while short-exponent obfuscators are on, else None"""
         return self._short[1] if self._short is not None else None
 
+    @property
+    def short_obfuscator_device_rng(self):
+        """True while the exponents of whole batches are ChaCha20 output under per-launch seeds (enable_short_obfuscators
+        (device_rng=True)), else False"""
+        return self._short is not None and self._short_rng
+
     def _draw_rho(self, eng, count):
-        """`count` fresh exponents as limb rows"""
+        """`count` fresh exponents as limb rows: from the kernel CSPRNG — or, for more than one row under the device_rng
+        setting, expanded from a fresh seed on the host (a lone row is 128 bytes: read directly)"""
         bits = self._short[1]
+        if self._short_rng and count > 1:
+            return _engine.seeded_bits_limbs(bits, count, (bits + 31) // 32)
         return _engine.random_bits_limbs(bits, count, (bits + 31) // 32)
 
     def _rho_limbs(self, rho_values, count, r_values=None):
