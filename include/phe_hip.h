@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 12
+#define PHE_HIP_ABI_VERSION 13
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -345,6 +345,26 @@ int phe_hip_fixed_base_pow_dev(phe_hip_ctx* ctx, const uint32_t* e, int exp_limb
  * one call).  rows == 0 is OK and launches nothing. */
 int phe_hip_chacha20_rows_dev(phe_hip_ctx* ctx, const uint32_t key[8], const uint32_t nonce[3], uint32_t counter0, int bits,
                               int limbs, uint32_t* out, size_t rows, void* stream);
+/* The planner of phe_hip_segment_reduce_dev on the device (csrc/segment_plan.h): the index arrays of the grouped sums from
+ * RESIDENT segment ids, element for element what the numpy planner (phe/_engine.py plan_segments: a stable argsort, a bincount,
+ * and per level a repeat, a cumsum and a second stable argsort) makes of the same ids on the host — the groups whose members'
+ * chains of EncryptedNumber.__add__ -> _raw_add (phe/paillier.py:705-719) the reduce kernel forms.
+ * phe_hip_segment_plan_sort_dev: ids (F, rows) int32 in [-1, S); node (rows) int32 in [-1, K) or NULL (K must then be 1).  Entry
+ * (f, i) belongs to output row (f*K + node[i])*S + ids[f][i]; an entry whose id or node is negative (or out of range) belongs to
+ * none.  idx_out (F*rows words): the row numbers i of the entries kept, by output row, within a row ascending (the sort is
+ * stable); the words behind the entries kept are unspecified.  counts_out (F*K*S + 1 words): the members of every output row,
+ * then the number of entries kept.  EINVAL: a null buffer, K == 0, S == 0 with rows > 0, F*rows >= 2^32, F*K*S > 2^32 - 2.
+ * phe_hip_segment_plan_level_dev: one level of tasks from `counts` (n_out words, on the device): per_out[k] = max(1,
+ * ceil(counts[k] / cap)) — the next level's counts —, task_ptr_out (tasks + 1): task t of row k starts at start[k] + (t *
+ * counts[k]) / per[k], the last entry is the sum of counts; order_out (tasks): the tasks longest first, equal lengths in task
+ * order.  `tasks` must be the sum of per_out, which the caller computes from a host copy of counts.  EINVAL: a null buffer,
+ * cap < 2, n_out == 0, tasks < n_out, n_out or tasks >= 2^32.
+ * Both calls keep their intermediates in the context's scratch, are ordered like every call on the context, use no atomic
+ * operation and give the same arrays on every run. */
+int phe_hip_segment_plan_sort_dev(phe_hip_ctx* ctx, const int32_t* ids, const int32_t* node, size_t F, size_t rows, size_t S,
+                                  size_t K, uint32_t* idx_out, uint32_t* counts_out, void* stream);
+int phe_hip_segment_plan_level_dev(phe_hip_ctx* ctx, const uint32_t* counts, size_t n_out, uint32_t cap, uint32_t* per_out,
+                                   uint64_t* task_ptr_out, uint32_t* order_out, size_t tasks, void* stream);
 /* max_exp_bits: upper bound on the bit length of every e[i] (0 = 32*exp_limbs) */
 int phe_hip_powmod_dev(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, int exp_limbs, int max_exp_bits,
                        uint32_t* out, size_t batch, void* stream);

@@ -34,6 +34,7 @@
 #include "slot_codec.h"
 #include "fixed_base.h"
 #include "chacha_rows.h"
+#include "segment_plan.h"
 #include "mul_io.h"
 #include "mul_table.h"
 #include "decrypt_tail.h"
@@ -139,6 +140,12 @@ int launch_fixed_base_pow(int G, int L, int blocks, hipStream_t st, const FixedB
 namespace rng {  // kernels_rng.hip
 int launch_chacha_rows(int blocks, hipStream_t st, const ChaChaRowsArgs& A);
 }  // namespace rng
+namespace plan {  // kernels_plan.hip
+void launch_plan_sort(int n_cus, hipStream_t st, const int32_t* ids, const int32_t* node, uint64_t F, uint64_t rows, uint32_t S,
+                      uint32_t K, uint32_t* idx_out, uint32_t* counts_out, uint32_t* scratch);
+void launch_plan_level(int n_cus, hipStream_t st, const uint32_t* counts, uint64_t n_out, uint32_t cap, uint32_t* per_out,
+                       uint64_t* task_ptr_out, uint32_t* order_out, uint64_t tasks, uint32_t* scratch);
+}  // namespace plan
 }  // namespace phe
 
 namespace phe {
@@ -2387,6 +2394,47 @@ int phe_hip_chacha20_rows_dev(phe_hip_ctx* ctx, const uint32_t key[8], const uin
     const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->n_cus * 8));
     phe::rng::launch_chacha_rows(blocks, (hipStream_t)stream, A);  // (the arguments are copied by the launch call)
     for (volatile uint32_t* w = A.key; w != A.key + 8; ++w) *w = 0;
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// ---- the device planner of the grouped sums (segment_plan.h, kernels_plan.hip) --------------------------------------------------
+// idx_out / counts_out from resident ids: a stable radix sort of (key, row) pairs and counts by binary search — the arrays that
+// phe/_engine.py plan_segments makes with argsort(kind="stable") and bincount, element for element.  The pairs, digit counts and
+// chunk totals live in the context's scratch.
+int phe_hip_segment_plan_sort_dev(phe_hip_ctx* ctx, const int32_t* ids, const int32_t* node, size_t F, size_t rows, size_t S, size_t K,
+                                  uint32_t* idx_out, uint32_t* counts_out, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    const uint64_t lim = (uint64_t)1 << 32;
+    if (!counts_out || (F && rows && (!ids || !idx_out))) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (K == 0 || (S == 0 && rows > 0)) return fail(PHE_HIP_EINVAL, "no segments for the rows given");
+    if ((uint64_t)F >= lim || (uint64_t)rows >= lim || (uint64_t)F * rows >= lim)
+        return fail(PHE_HIP_EINVAL, "F * rows must be below 2^32: row numbers and positions are 32-bit");
+    if ((uint64_t)S >= lim || (uint64_t)K >= lim || (uint64_t)K * S >= lim || (uint64_t)F * ((uint64_t)K * S) > 0xFFFFFFFEull)
+        return fail(PHE_HIP_EINVAL, "F * K * S must not exceed 2^32 - 2: keys are 32-bit");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    if (int rc = ensure_words(&ctx->scratch, &ctx->scratch_words, (size_t)std::max<uint64_t>(1, phe::plan::plan_sort_words((uint64_t)F * rows))))
+        return rc;
+    phe::plan::launch_plan_sort(ctx->n_cus, (hipStream_t)stream, ids, node, F, rows, (uint32_t)S, (uint32_t)K, idx_out, counts_out,
+                                ctx->scratch);
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// One level of tasks from the level's counts (segment_plan.h plan_level): per_out, task_ptr_out and order_out as plan_segments
+// makes them with repeat, cumsum and argsort(-lengths, kind="stable").  `tasks` is what the caller summed from the same counts.
+int phe_hip_segment_plan_level_dev(phe_hip_ctx* ctx, const uint32_t* counts, size_t n_out, uint32_t cap, uint32_t* per_out,
+                                   uint64_t* task_ptr_out, uint32_t* order_out, size_t tasks, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (!counts || !per_out || !task_ptr_out || !order_out) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (cap < 2) return fail(PHE_HIP_EINVAL, "a task must be allowed at least two rows");
+    if (n_out == 0 || (uint64_t)n_out >= ((uint64_t)1 << 32) || tasks < n_out || (uint64_t)tasks >= ((uint64_t)1 << 32))
+        return fail(PHE_HIP_EINVAL, "rows and tasks of a level: 1 <= n_out <= tasks < 2^32");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    if (int rc = ensure_words(&ctx->scratch, &ctx->scratch_words, (size_t)phe::plan::plan_level_words(n_out, tasks))) return rc;
+    phe::plan::launch_plan_level(ctx->n_cus, (hipStream_t)stream, counts, n_out, cap, per_out, task_ptr_out, order_out, tasks, ctx->scratch);
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;
 }

@@ -226,6 +226,46 @@ class SegmentPlan:
     def __init__(self, levels, n_out):
         self.levels, self.n_out = levels, n_out
 
+    @property
+    def tasks(self):
+        """tasks of every level"""
+        return [len(order) for _, _, order in self.levels]
+
+    @property
+    def n_idx(self):
+        """entries of level 0's idx: the (grouping, row) pairs that belong to a segment"""
+        return len(self.levels[0][1])
+
+
+# The numpy planner below (a stable argsort, a bincount, per level a repeat, a cumsum and a second argsort, then the index arrays
+# going up) takes 14.1 - 15.8 ms for one grouping of 2^20 rows and 135 - 138 ms for eight; Engine.plan_segments_dev makes the same
+# arrays on the device in 0.29 - 0.30 / 0.57 - 0.61 ms.  Its route costs some twenty launches and one small download however few
+# the ids are, so EncryptedVector.segment_sum keeps the numpy planner below this many (grouping, row) pairs.  Measured with
+# tools/bench_segment_plan.py (profiles/r14_segment_plan.json: planning alone, one grouping, 256 segments, F * rows = 2^10 ...
+# 2^24 in powers of four, host / device in ms): 0.11 - 0.12 / 0.10 - 0.12 at 2^10 (a tie), 0.19 - 0.21 / 0.14 - 0.16 at 2^12,
+# 0.25 - 0.28 / 0.15 at 2^14, 0.54 - 0.58 / 0.19 - 0.20 at 2^16, 2.05 - 2.13 / 0.19 - 0.21 at 2^18, 8.8 - 9.8 / 0.28 - 0.30 at
+# 2^20, 74 - 77 / 0.39 - 0.43 at 2^22, 353 - 359 / 0.87 - 0.90 at 2^24.  2^12 is the crossover: the smallest size from which on
+# the device route's slowest repeat is not above the host route's fastest.
+SEGMENT_PLAN_DEVICE_MIN = 1 << 12
+
+
+class DeviceSegmentPlan:
+    """A SegmentPlan made and kept on the device (Engine.plan_segments_dev): `dev` is what Engine.segment_upload returns for a
+    host plan — [(task_ptr, idx or None, order) DeviceArrays, ...] —, `tasks` the tasks of every level and `n_idx` the entries of
+    idx that count (the block behind them is as long as the ids and its tail unspecified)."""
+
+    def __init__(self, dev, tasks, n_out, n_idx):
+        self.dev, self.tasks, self.n_out, self.n_idx = dev, tasks, n_out, n_idx
+
+    def to_host(self):
+        """the plan as a SegmentPlan of numpy arrays (tests, measurements)"""
+        levels = []
+        for (tp, idx, order), tasks in zip(self.dev, self.tasks):
+            levels.append((tp.to_host().reshape(-1).view(np.uint64)[:tasks + 1].copy(),
+                           idx.to_host().reshape(-1)[:self.n_idx].copy() if idx is not None else None,
+                           order.to_host().reshape(-1)[:tasks].copy()))
+        return SegmentPlan(levels, self.n_out)
+
 
 def plan_segments(seg_ids, n_segments, cap=None):
     """seg_ids: (rows,) integers in [-1, n_segments) — -1 leaves the row out — or (F, rows): F groupings of the same rows, whose
@@ -929,21 +969,81 @@ class Engine:
             return DeviceArray(self.ctx, 0, self.pair_form() if want_pair else self.ct_limbs)
         return self.segment_launch_dev(store, is_pair, plan, self.segment_upload(plan), want_pair)
 
+    def segment_reduce_ids_dev(self, store, is_pair, ids_dev, n_segments, node_dev=None, n_nodes=1, want_pair=False):
+        """segment_reduce_dev over ids that are resident already (plan_segments_dev): nothing but the members of every output row
+        comes down, nothing goes up"""
+        plan = self.plan_segments_dev(ids_dev, n_segments, node_dev, n_nodes, SEGMENT_TASK_ROWS)
+        if plan.n_out == 0:
+            return DeviceArray(self.ctx, 0, self.pair_form() if want_pair else self.ct_limbs)
+        return self.segment_launch_dev(store, is_pair, plan, plan.dev, want_pair)
+
+    def upload_ids(self, ids):
+        """integers that fit 32 bits (validated segment ids, node numbers) as resident int32: (F, rows), or (rows, 1) from (rows,)"""
+        return DeviceArray.from_host(self.ctx, np.ascontiguousarray(ids, dtype=np.int32).view(np.uint32))
+
     def segment_upload(self, plan):
         """the index arrays of every level of a SegmentPlan as device blocks: [(task_ptr, idx or None, order), ...]"""
         return [(DeviceArray.from_host(self.ctx, task_ptr.view(np.uint32).reshape(-1, 2)),
                  DeviceArray.from_host(self.ctx, idx) if idx is not None else None,
                  DeviceArray.from_host(self.ctx, order)) for task_ptr, idx, order in plan.levels]
 
+    # ---- the planner on the device (include/phe_hip.h phe_hip_segment_plan_sort_dev / _level_dev) --------------------------
+    def has_segment_planner(self):
+        """True when the backend plans grouped sums from resident ids"""
+        return hasattr(self.ctx, "segment_plan_sort_dev") and hasattr(self.ctx, "segment_plan_level_dev")
+
+    @staticmethod
+    def segment_planner_fits(groupings, rows, n_out):
+        """the sizes the device planner takes: 32-bit positions and keys, one key to spare for the entries left out"""
+        return groupings * rows < 1 << 32 and n_out <= (1 << 32) - 2
+
+    def plan_segments_dev(self, ids_dev, n_segments, node_dev=None, n_nodes=1, cap=None):
+        """plan_segments on the device -> DeviceSegmentPlan.  ids_dev: a DeviceArray of shape (F, rows) holding int32 ids in
+        [-1, n_segments); node_dev: (rows, 1) int32 in [-1, n_nodes) or None.  Output row (f * n_nodes + node[i]) * n_segments +
+        ids[f][i]; an entry whose id or node is -1 belongs to none.  Every level's task_ptr, idx and order are element for
+        element those of plan_segments(where((node >= 0) & (ids >= 0), node * n_segments + ids, -1), n_nodes * n_segments, cap).
+        One download: the members of every output row, from which the host sizes the levels."""
+        cap = int(SEGMENT_TASK_ROWS if cap is None else cap)
+        if cap < 2:
+            raise ValueError("a task must be allowed at least two rows")
+        f, n = ids_dev.rows, ids_dev.cols
+        n_out = f * int(n_nodes) * int(n_segments)
+        if n_out == 0:                                       # no output rows: nothing to sort, the plan is one empty level
+            plan = plan_segments(np.full((max(f, 1), n), -1, np.int64), 0, cap)
+            return DeviceSegmentPlan(self.segment_upload(plan), plan.tasks, 0, 0)
+        if not self.segment_planner_fits(f, n, n_out):
+            raise ValueError("the device planner takes F * rows < 2^32 and at most 2^32 - 2 output rows")
+        idx = DeviceArray(self.ctx, max(1, f * n), 1)
+        counts_d = DeviceArray(self.ctx, n_out + 1, 1)
+        self.ctx.segment_plan_sort_dev(ids_dev.ptr, node_dev.ptr if node_dev is not None else None, f, n, int(n_segments),
+                                       int(n_nodes), idx.ptr, counts_d.ptr)
+        host = counts_d.to_host().reshape(-1)
+        counts, n_idx = host[:n_out].astype(np.int64), int(host[n_out])
+        dev, tasks_of, alive = [], [], []
+        while True:
+            per = np.maximum(1, -(-counts // cap))
+            tasks = int(per.sum())
+            if tasks >= 1 << 32:
+                raise ValueError("the device planner takes fewer than 2^32 tasks per level")
+            per_d, tp_d, order_d = DeviceArray(self.ctx, n_out, 1), DeviceArray(self.ctx, tasks + 1, 2), DeviceArray(self.ctx, tasks, 1)
+            self.ctx.segment_plan_level_dev(counts_d.ptr, n_out, cap, per_d.ptr, tp_d.ptr, order_d.ptr, tasks)
+            dev.append((tp_d, idx if not dev else None, order_d))
+            tasks_of.append(tasks)
+            if int(per.max()) <= 1:
+                self.ctx.sync()                              # (counts_d / per_d of the levels are read until here)
+                return DeviceSegmentPlan(dev, tasks_of, n_out, n_idx)
+            alive.append(counts_d)                           # (a level's counts stay allocated while its launches may run)
+            counts, counts_d = per, per_d
+
     def segment_launch_dev(self, store, is_pair, plan, dev, want_pair=False):
-        """the levels of an uploaded plan (segment_upload) over `store`, queued back to back; one synchronisation"""
+        """the levels of a plan over `store`, queued back to back; one synchronisation.  plan: a SegmentPlan with `dev` what
+        segment_upload made of it, or a DeviceSegmentPlan with its own `dev`"""
         words = self.pair_form()
-        if not is_pair and len(plan.levels[0][1]) > store.rows > 0:
+        if not is_pair and plan.n_idx > store.rows > 0:
             store, is_pair = self.to_pair_dev(store), True   # several groupings read every row: into the form once, not F times
         keep = [store]                                       # operands stay alive until the final synchronisation
         rows, rows_are_pair, n_rows = store, is_pair, store.rows
-        for (_, _, order), (tp_d, idx_d, order_d) in zip(plan.levels, dev):
-            tasks = len(order)
+        for tasks, (tp_d, idx_d, order_d) in zip(plan.tasks, dev):
             out = DeviceArray(self.ctx, tasks, words)
             self.ctx.segment_reduce_dev(rows.ptr, rows_are_pair, n_rows, tp_d.ptr, idx_d.ptr if idx_d is not None else None,
                                         order_d.ptr, out.ptr, tasks)

@@ -18,7 +18,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("PHE_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libphe_hip.so")
 
 OK, EINVAL, EHIP, ENOINVERSE = 0, 1, 2, 3
-ABI_VERSION = 12         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
+ABI_VERSION = 13         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
 
 _lib = None
 
@@ -115,6 +115,8 @@ def lib():
         L.phe_hip_segment_reduce_dev.argtypes = [vp, vp, ci, sz, vp, vp, vp, vp, sz, vp]
         L.phe_hip_segment_scan_dev.argtypes = [vp, vp, ci, sz, vp, vp, vp, vp, sz, vp]
         L.phe_hip_segment_pack_dev.argtypes = [vp, vp, ci, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
+        L.phe_hip_segment_plan_sort_dev.argtypes = [vp, vp, vp, sz, sz, sz, sz, vp, vp, vp]
+        L.phe_hip_segment_plan_level_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, sz, vp]
         L.phe_hip_slots_pack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
         L.phe_hip_slots_unpack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
         L.phe_hip_fixed_base_set.argtypes = [vp, vp, ci, ci]
@@ -147,7 +149,7 @@ EXPORTED_SYMBOLS = [
     "phe_hip_pair_powmod_dev", "phe_hip_pair_multiexp_rows_dev", "phe_hip_segment_reduce_dev",
     "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev", "phe_hip_slots_pack_dev", "phe_hip_slots_unpack_dev",
     "phe_hip_fixed_base_set", "phe_hip_fixed_base_info", "phe_hip_fixed_base_clear", "phe_hip_fixed_base_rows_dev",
-    "phe_hip_fixed_base_pow_dev", "phe_hip_chacha20_rows_dev",
+    "phe_hip_fixed_base_pow_dev", "phe_hip_chacha20_rows_dev", "phe_hip_segment_plan_sort_dev", "phe_hip_segment_plan_level_dev",
 ]
 
 
@@ -394,6 +396,16 @@ class Context:
         """out[t] (pair rows) = prod_j rows[t*slots + j] ^ (2^(slot_bits*j)) (include/phe_hip.h phe_hip_segment_pack_dev)"""
         _check(lib().phe_hip_segment_pack_dev(self._h, rows_ptr, 1 if rows_are_pair else 0, n_rows, slots, slot_bits, out_ptr, tasks,
                                               stream))
+
+    def segment_plan_sort_dev(self, ids_ptr, node_ptr, groupings, rows, n_segments, n_nodes, idx_ptr, counts_ptr, stream=0):
+        """idx (groupings * rows words) and counts (groupings * n_nodes * n_segments + 1 words) of the grouped sums from resident
+        int32 ids (include/phe_hip.h phe_hip_segment_plan_sort_dev); node_ptr None: no node array"""
+        _check(lib().phe_hip_segment_plan_sort_dev(self._h, ids_ptr, node_ptr, groupings, rows, n_segments, n_nodes, idx_ptr,
+                                                   counts_ptr, stream))
+
+    def segment_plan_level_dev(self, counts_ptr, n_out, cap, per_ptr, task_ptr, order_ptr, tasks, stream=0):
+        """per, task_ptr and order of one level from the level's counts (include/phe_hip.h phe_hip_segment_plan_level_dev)"""
+        _check(lib().phe_hip_segment_plan_level_dev(self._h, counts_ptr, n_out, cap, per_ptr, task_ptr, order_ptr, tasks, stream))
 
     # ---- powers of one fixed base by short exponents (include/phe_hip.h phe_hip_fixed_base_*) ----
     def fixed_base_set(self, hs, exp_bits, window=0):

@@ -8,8 +8,11 @@ EncryptedVector is the batched sibling the GPU actually wants: one (batch, ct_li
 plus per-element exponents and obfuscation flags; `+`, `*`, obfuscate(), decrease_exponent_to() are one
 kernel launch each over the whole vector, with the same per-element semantics as EncryptedNumber.
 """
+import weakref
+
 import numpy as np
 
+from . import _engine
 from ._device import DeviceArray
 from ._engine import _ranges, random_lt_n, random_lt_n_limbs
 from .codec import EncodedNumber
@@ -153,6 +156,80 @@ class EncryptedNumber(object):
 def _fleet_min_rows():
     from . import fleet
     return fleet.MIN_ROWS_PER_DEVICE
+
+
+def _checked_segment_ids(segment_ids, num_segments, length):
+    """(ids as int64 of shape (length,) or (F, length), num_segments) or the errors of EncryptedVector.segment_sum; length None:
+    any"""
+    ids = np.asarray(segment_ids)
+    if ids.size == 0:
+        ids = ids.astype(np.int64)
+    if ids.dtype.kind not in "iu":
+        raise TypeError("segment_ids must be integers")
+    if length is None:
+        if ids.ndim not in (1, 2):
+            raise ValueError("segment_ids must have shape (rows,) or (F, rows)")
+    elif ids.ndim not in (1, 2) or ids.shape[-1] != length:
+        raise ValueError("segment_ids must have shape (%d,) or (F, %d)" % (length, length))
+    ids = ids.astype(np.int64)
+    if num_segments is None:
+        num_segments = int(ids.max()) + 1 if ids.size else 0
+    num_segments = int(num_segments)
+    if num_segments < 0:
+        raise ValueError("num_segments must not be negative")
+    bad = np.nonzero((ids.ravel() < -1) | (ids.ravel() >= num_segments))[0]
+    if len(bad):
+        raise ValueError("segment id %d is outside [0, %d) and is not -1" % (int(ids.ravel()[bad[0]]), num_segments))
+    return ids, num_segments
+
+
+def _checked_nodes(node, num_nodes, length):
+    """(node as int64 of shape (length,), num_nodes): one node number in [-1, num_nodes) per element"""
+    node = np.asarray(node)
+    if node.size == 0:
+        node = node.astype(np.int64)
+    if node.dtype.kind not in "iu":
+        raise TypeError("node must be integers")
+    if node.ndim != 1 or node.shape[0] != length:
+        raise ValueError("node must have shape (%d,)" % length)
+    node = node.astype(np.int64)
+    if num_nodes is None:
+        num_nodes = int(node.max()) + 1 if node.size else 0
+    num_nodes = int(num_nodes)
+    if num_nodes < 0:
+        raise ValueError("num_nodes must not be negative")
+    bad = np.nonzero((node < -1) | (node >= num_nodes))[0]
+    if len(bad):
+        raise ValueError("node %d is outside [0, %d) and is not -1" % (int(node[bad[0]]), num_nodes))
+    return node, num_nodes
+
+
+class ResidentSegmentIds(object):
+    """Segment ids for EncryptedVector.segment_sum, validated once and kept on the device (PaillierPublicKey.segment_ids): the
+    bin of every sample per feature stays what it is for a whole training run, while the node array changes with every call.
+    `ids` is the validated host copy (int32; what a backend without the device planner plans from), `shape` its shape,
+    `num_segments` the bound it was checked against.  The resident copy is made on first use, one per engine of the key (a
+    fleet's devices each get their own)."""
+
+    def __init__(self, public_key, segment_ids, num_segments=None):
+        ids, num_segments = _checked_segment_ids(segment_ids, num_segments, None)
+        if num_segments >= 1 << 31:
+            raise ValueError("resident segment ids are 32-bit")
+        self.public_key = public_key
+        self.ids = np.ascontiguousarray(ids, dtype=np.int32)
+        self.ids.setflags(write=False)
+        self.shape, self.num_segments = self.ids.shape, num_segments
+        self._resident = weakref.WeakKeyDictionary()
+
+    def on(self, eng):
+        """the ids as a resident (F, rows) int32 block of this engine's device"""
+        dev = self._resident.get(eng)
+        if dev is None:
+            dev = self._resident[eng] = eng.upload_ids(self.ids if self.ids.ndim == 2 else self.ids[None, :])
+        return dev
+
+    def __len__(self):
+        return self.shape[-1]
 
 
 class EncryptedVector(object):
@@ -619,7 +696,7 @@ class EncryptedVector(object):
             limbs = np.concatenate([merged, limbs[2 * half:]]) if limbs.shape[0] % 2 else merged
         return EncryptedNumber(pk, eng.to_ints(limbs)[0], exp)
 
-    def segment_sum(self, segment_ids, num_segments=None):
+    def segment_sum(self, segment_ids, num_segments=None, node=None, num_nodes=None):
         """Homomorphic sums BY GROUP -> EncryptedVector of `num_segments` rows: row s is the sum of the elements i with
         segment_ids[i] == s — np.bincount(segment_ids, weights=x) on ciphertexts; the gradient histograms of federated
         boosting, per-class aggregation, group-by.  segment_ids: len(self) integers in any order, -1 leaves an element out,
@@ -633,29 +710,53 @@ class EncryptedVector(object):
         One limb group walks the rows of a segment with the running product in registers (Engine.segment_reduce_dev): one
         pair product per element.  A resident vector gives a resident result (in the pair form if the vector is in it); a
         host vector goes up, through the same kernel, and back.  Without that kernel (no split-modulus engine for the key
-        width) the sums are formed by rounds of element-wise products over the gathered halves of every group: same bits."""
+        width) the sums are formed by rounds of element-wise products over the gathered halves of every group: same bits.
+        node: len(self) integers in [-1, num_nodes) (num_nodes defaults to max + 1), checked like the ids — the tree node every
+        element is in, -1 for none.  The result is BY DEFINITION segment_sum(np.where((node >= 0) & (segment_ids >= 0),
+        node * num_segments + segment_ids, -1), num_nodes * num_segments): row f * num_nodes * num_segments + k * num_segments + s
+        — the histograms of every node of a tree level from one call, with the bins of the samples unchanged.
+        segment_ids may be a ResidentSegmentIds (PaillierPublicKey.segment_ids): ids validated once and kept on the device.
+        From _engine.SEGMENT_PLAN_DEVICE_MIN (grouping, element) pairs on, the index arrays of the kernel are made on the device
+        too (Engine.plan_segments_dev: the same arrays as the numpy planner's, so the same bits); with resident ids only `node`
+        then crosses PCIe."""
         pk = self.public_key
-        ids = np.asarray(segment_ids)
-        if ids.size == 0:
-            ids = ids.astype(np.int64)
-        if ids.dtype.kind not in "iu":
-            raise TypeError("segment_ids must be integers")
-        if ids.ndim not in (1, 2) or ids.shape[-1] != len(self):
-            raise ValueError("segment_ids must have shape (%d,) or (F, %d)" % (len(self), len(self)))
-        ids = ids.astype(np.int64)
-        if num_segments is None:
-            num_segments = int(ids.max()) + 1 if ids.size else 0
-        num_segments = int(num_segments)
-        if num_segments < 0:
-            raise ValueError("num_segments must not be negative")
-        bad = np.nonzero((ids.ravel() < -1) | (ids.ravel() >= num_segments))[0]
-        if len(bad):
-            raise ValueError("segment id %d is outside [0, %d) and is not -1" % (int(ids.ravel()[bad[0]]), num_segments))
-        n_out = (ids.shape[0] if ids.ndim == 2 else 1) * num_segments
+        resident = segment_ids if isinstance(segment_ids, ResidentSegmentIds) else None
+        if resident is not None:
+            if resident.public_key != pk:
+                raise ValueError("these segment ids were made for another key")
+            if resident.shape[-1] != len(self):
+                raise ValueError("segment_ids must have shape (%d,) or (F, %d)" % (len(self), len(self)))
+            if num_segments is not None and int(num_segments) != resident.num_segments:
+                raise ValueError("these segment ids were made for %d segments" % resident.num_segments)
+            ids, num_segments = resident.ids, resident.num_segments
+        else:
+            ids, num_segments = _checked_segment_ids(segment_ids, num_segments, len(self))
+        if node is not None:
+            node, num_nodes = _checked_nodes(node, num_nodes, len(self))
+        elif num_nodes is not None:
+            raise ValueError("num_nodes needs a node array")
+        groupings = ids.shape[0] if ids.ndim == 2 else 1
+        nodes = num_nodes if node is not None else 1
+        n_out = groupings * nodes * num_segments
         eng = self._eng()
         exp = int(self._exps.min()) if len(self) else 0
         cur = self.decrease_exponent_to(exp) if len(self) else self
         exps = np.full(n_out, exp, dtype=np.int64)
+        if (eng.has_segment_reduce() and eng.has_segment_planner() and groupings * len(self) >= _engine.SEGMENT_PLAN_DEVICE_MIN
+                and eng.segment_planner_fits(groupings, len(self), n_out) and max(num_segments, nodes) < 1 << 31):
+            # the plan is made where the rows are: the ids go up as int32 (or are there already), the node numbers with them
+            ids_dev = resident.on(eng) if resident is not None else eng.upload_ids(ids if ids.ndim == 2 else ids[None, :])
+            node_dev = eng.upload_ids(node) if node is not None else None
+            if self.on_device:
+                store = cur._store if cur._pair else cur._plain_rows()
+                out = eng.segment_reduce_ids_dev(store, cur._pair, ids_dev, num_segments, node_dev, nodes, want_pair=self._pair)
+                return EncryptedVector(pk, out, exps, _pair=self._pair)
+            out = eng.segment_reduce_ids_dev(eng.upload_cipher(cur._limbs), False, ids_dev, num_segments, node_dev, nodes)
+            return EncryptedVector(pk, out.to_host(), exps)
+        if node is not None:                                       # the definition of node=, on the host
+            ids = np.where((node >= 0) & (ids >= 0), node * num_segments + ids, -1)
+            num_segments = num_nodes * num_segments
+        ids = ids.astype(np.int64)
         if eng.has_segment_reduce():
             if self.on_device:
                 store = cur._store if cur._pair else cur._plain_rows()

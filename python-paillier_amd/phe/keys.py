@@ -511,6 +511,15 @@ class PaillierPublicKey(object):
             ms = [sum(x << (B * j) for j, x in enumerate(xs[b * S:(b + 1) * S])) % n for b in range(rows)]
         return _native.ints_to_limbs(ms, n_limbs)
 
+    def segment_ids(self, ids, num_segments=None):
+        """Segment ids for EncryptedVector.segment_sum under this key, validated once and kept on the device ->
+        ResidentSegmentIds.  ids: integers of shape (rows,) or (F, rows) in [-1, num_segments) (num_segments defaults to
+        max + 1; TypeError / ValueError as segment_sum raises them).  The bins of a training set stay the same from node to
+        node: pass the object in place of the ids and, from the sizes on at which the plan is made on the device, only the
+        `node` array of a call crosses PCIe.  The upload happens on first use, once per device of a fleet."""
+        from .ciphertext import ResidentSegmentIds
+        return ResidentSegmentIds(self, ids, num_segments)
+
     def encrypt_packed(self, values, slots, slot_bits, precision=None, r_values=None, device=False, rho_values=None):
         """Encode, PACK and encrypt -> EncryptedVector of ceil(len(values) / slots) rows: row b encrypts
         V_b = x[b*S] + x[b*S + 1] * 2^B + x[b*S + 2] * 2^(2B) + ... (S = slots, B = slot_bits) for the signed mantissas x of the
