@@ -57,7 +57,7 @@ const char* phe_hip_last_error(void);
  * it mirrors before the first call (phe/_native.py lib()): argument lists changed under unchanged symbol names twice
  * (round 5: phe_hip_gather_rows_dev / phe_hip_scatter_rows_dev gained a row-count bound), and a stale mirror would still link.
  * Bumped on every change to an existing signature or to the meaning of an argument; new entry points alone do not bump it. */
-#define PHE_HIP_ABI_VERSION 13
+#define PHE_HIP_ABI_VERSION 14
 int phe_hip_abi_version(void);
 
 /* Number of visible HIP devices. */
@@ -315,6 +315,25 @@ int phe_hip_slots_pack_dev(phe_hip_ctx* ctx, const int64_t* values, size_t count
                            uint32_t* m_rows, size_t rows, void* stream);
 int phe_hip_slots_unpack_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t rows, uint32_t slots, uint32_t slot_bits,
                              int64_t* values, uint8_t* status, void* stream);
+/* The value codec of plain batches (csrc/value_codec.h): one value per plaintext row, formed and read where the rows live.  Both
+ * kernels are bound by memory.  The key must have max_int >= 2^64 (EINVAL otherwise), so that every 64-bit magnitude is a valid
+ * plaintext.
+ * encode replaces EncodedNumber.encode (phe/encoding.py:110-199) for arrays: bits holds the raw 64-bit words of `count` values,
+ * kind says what they are — 0: int64, 1: uint64 (both exponent 0), 2: float64 at its natural exponent
+ * floor((frexp exponent - 53) / 4) with the 53-bit mantissa shifted by the remainder, 3: float64 under a precision, ALL at the
+ * `exponent` given (floor(log16 precision), within [-300, 300]) with the mantissa rint(x * 16^-exponent), ties to even.
+ * m_rows[i] (count x n_limbs words) = mantissa mod n (a negative zero gives 0), exps[i] = the exponent (written for kind 2 only;
+ * may be null otherwise), status[i] = 0, or 1: inf / nan, or 2: kind 3 and |mantissa| >= 2^62 (the caller encodes on the host).
+ * decode replaces EncodedNumber.decode (phe/encoding.py:201-233): out[i] = the number m_rows[i] stands for (m if m <= max_int,
+ * m - n if m >= n - max_int) as an int64 (kind 0) or as the float64 +-(double)|v| * 16^exps[i] (kind 1; the conversion rounds to
+ * nearest even and the scaling is exact for -240 <= exps[i] < 0: the caller sends no others), status[i] = 0, or 1: m lies
+ * between the two ranges (the overflow of :221), or 2: |v| >= 2^64 or, for kind 0, v outside int64 (the caller decodes that row
+ * on the host), or 3: m >= n (the corrupted number of :213); out[i] of a row with a non-zero status is unspecified.
+ * An unknown kind, a null buffer, a key below the bound: EINVAL. */
+int phe_hip_values_encode_dev(phe_hip_ctx* ctx, const uint64_t* bits, size_t count, uint32_t kind, int32_t exponent,
+                              uint32_t* m_rows, int32_t* exps, uint8_t* status, void* stream);
+int phe_hip_values_decode_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t rows, uint32_t kind, const int32_t* exps,
+                              uint64_t* out, uint8_t* status, void* stream);
 /* Powers of ONE base by many short exponents (csrc/fixed_base.h): the short-exponent obfuscators h_s^rho of
  * PaillierPublicKey.enable_short_obfuscators.  A fixed-base comb: with the exponent cut into T = ceil(exp_bits / window) digits,
  * hs^e is the product of T entries of a table of T * (2^window - 1) pair rows, entry (t, d) = hs^(d * 2^(window t)) at row

@@ -32,6 +32,7 @@
 #include "split_core.h"
 #include "segment_core.h"
 #include "slot_codec.h"
+#include "value_codec.h"
 #include "fixed_base.h"
 #include "chacha_rows.h"
 #include "segment_plan.h"
@@ -134,6 +135,10 @@ namespace slots {  // kernels_slots.hip
 int launch_slots_pack(int G, int K, int blocks, hipStream_t st, const SlotPackArgs& A);
 int launch_slots_unpack(int G, int K, int blocks, hipStream_t st, const SlotUnpackArgs& A);
 }  // namespace slots
+namespace values {  // kernels_values.hip
+int launch_values_encode(int G, int K, int blocks, hipStream_t st, const ValueEncodeArgs& A);
+int launch_values_decode(int G, int K, int blocks, hipStream_t st, const ValueDecodeArgs& A);
+}  // namespace values
 namespace fb {  // kernels_fb.hip
 int launch_fixed_base_pow(int G, int L, int blocks, hipStream_t st, const FixedBaseArgs& A, bool mul_is_residue, bool exit);
 }  // namespace fb
@@ -2528,6 +2533,73 @@ int phe_hip_slots_unpack_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t ro
     A.n_limbs = ctx->pub.s1;
     if (phe::slots::launch_slots_unpack(G, K, grid_blocks(ctx, rows, G, 8), (hipStream_t)stream, A) < 0)
         return fail(PHE_HIP_EINVAL, "no slot codec kernel for this key width");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// ---- the value codec of plain batches (value_codec.h, kernels_values.hip) ------------------------------------------------------
+// the checks both entries share; G, K: the geometry of the key's plaintext rows
+static int values_check(const phe_hip_ctx* ctx, uint32_t kind, uint32_t kinds, int& G, int& K) {
+    if (kind >= kinds) return fail(PHE_HIP_EINVAL, "unknown kind " + std::to_string(kind));
+    if (!host::value_codec_key_ok(ctx->pub.n.data(), ctx->pub.s1))
+        return fail(PHE_HIP_EINVAL, "the value codec needs a key with max_int >= 2^64");
+    if (!host::slot_geometry(ctx->pub.s1, G, K)) return fail(PHE_HIP_EINVAL, "no value codec kernel for this key width");
+    return PHE_HIP_OK;
+}
+
+// m_rows[i] = the plaintext of value i as EncodedNumber.encode picks it (phe/encoding.py:110-199), exps[i] its exponent
+// (value_codec.h values_encode_body)
+int phe_hip_values_encode_dev(phe_hip_ctx* ctx, const uint64_t* bits, size_t count, uint32_t kind, int32_t exponent,
+                              uint32_t* m_rows, int32_t* exps, uint8_t* status, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    int G = 0, K = 0;
+    if (int rc = values_check(ctx, kind, 4, G, K)) return rc;
+    if (kind == kValueFloatPrecision && (exponent < -300 || exponent > 300))
+        return fail(PHE_HIP_EINVAL, "the exponent of a precision must lie in [-300, 300]");
+    if (count == 0) return PHE_HIP_OK;
+    if (!bits || !m_rows || !status || (kind == kValueFloat && !exps)) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    SlotConsts k;
+    if (int rc = slots_consts(ctx, 0, 0, G * K, k)) return rc;  // (no slots: the rows n, max_int and n - max_int)
+    ValueEncodeArgs A;
+    A.n = k.n;
+    A.bits = bits;
+    A.count = count;
+    A.kind = kind;
+    A.exponent = exponent;
+    A.m_rows = m_rows;
+    A.exps = exps;
+    A.status = status;
+    A.n_limbs = ctx->pub.s1;
+    if (phe::values::launch_values_encode(G, K, grid_blocks(ctx, count, G, 8), (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "no value codec kernel for this key width");
+    HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// out[i] = the number the plaintext row m_rows[i] stands for at exps[i], as EncodedNumber.decode returns it
+// (phe/encoding.py:201-233), status[i] = 0 or why not (value_codec.h values_decode_body)
+int phe_hip_values_decode_dev(phe_hip_ctx* ctx, const uint32_t* m_rows, size_t rows, uint32_t kind, const int32_t* exps,
+                              uint64_t* out, uint8_t* status, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    int G = 0, K = 0;
+    if (int rc = values_check(ctx, kind, 2, G, K)) return rc;
+    if (rows == 0) return PHE_HIP_OK;
+    if (!m_rows || !out || !status || (kind == kDecodeFloat && !exps)) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (int rc = bind_device(ctx)) return rc;
+    PHE_CTX_ORDER(ctx, stream);
+    ValueDecodeArgs A;
+    if (int rc = slots_consts(ctx, 0, 0, G * K, A.k)) return rc;
+    A.m_rows = m_rows;
+    A.rows = rows;
+    A.kind = kind;
+    A.exps = exps;
+    A.out = out;
+    A.status = status;
+    A.n_limbs = ctx->pub.s1;
+    if (phe::values::launch_values_decode(G, K, grid_blocks(ctx, rows, G, 8), (hipStream_t)stream, A) < 0)
+        return fail(PHE_HIP_EINVAL, "no value codec kernel for this key width");
     HIP_TRY(hipGetLastError());
     return PHE_HIP_OK;
 }

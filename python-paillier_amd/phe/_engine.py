@@ -1215,6 +1215,137 @@ class Engine:
             running.clear()
             staged.clear()
 
+    # ---- the value codec of plain batches (include/phe_hip.h phe_hip_values_encode_dev / phe_hip_values_decode_dev) -------------
+    VALUE_KINDS = {"i": 0, "u": 1, "f": 2}                 # numpy dtype kind -> `kind` of the encode kernel (3: float + precision)
+
+    def has_value_codec(self):
+        """True when the backend has both entries of the value codec and the key leaves room for every 64-bit magnitude"""
+        return (hasattr(self.ctx, "values_encode_dev") and hasattr(self.ctx, "values_decode_dev")
+                and self.n_limbs >= 4 and self.max_int >= 1 << 64)
+
+    def values_encode_dev(self, array, precision_exponent=None):
+        """int64 / uint64 / float64 array -> (RESIDENT plaintext rows, exponents): row i is the encoding
+        EncodedNumber.encode picks for array[i], formed on the device from the 8 bytes of the value.  The exponents come back
+        as an int64 array on the host — or, with precision_exponent (float64 only: every value at that one exponent, the
+        mantissa rounded half to even), as that integer.  inf / nan: ValueError.  None when a mantissa under a precision
+        reaches 2^62: the caller encodes on the host."""
+        array = np.ascontiguousarray(array).reshape(-1)
+        if array.dtype.kind not in self.VALUE_KINDS or array.dtype.itemsize != 8:
+            raise TypeError("the value codec takes int64, uint64 and float64 arrays, not %s" % array.dtype)
+        kind = self.VALUE_KINDS[array.dtype.kind]
+        if precision_exponent is not None:
+            if kind != 2:
+                raise TypeError("a precision applies to float64 arrays")
+            kind = 3
+        count = len(array)
+        out = DeviceArray(self.ctx, count, self.n_limbs)
+        if kind == 2:
+            exps = np.empty(count, dtype=np.int64)
+        elif kind == 3:
+            exps = int(precision_exponent)
+        else:
+            exps = np.zeros(count, dtype=np.int64)
+        if count == 0:
+            return out, exps
+        bits = DeviceArray.from_host(self.ctx, array.view(np.uint32))        # (a 64-bit word is two)
+        stat = DeviceArray(self.ctx, (count + 3) // 4, 1)
+        e_dev = DeviceArray(self.ctx, count, 1) if kind == 2 else None
+        self.ctx.values_encode_dev(bits.ptr, count, kind, exps if kind == 3 else 0, out.ptr, e_dev.ptr if e_dev else None, stat.ptr)
+        self.ctx.sync()
+        status = np.empty(count, dtype=np.uint8)
+        self.ctx.d2h(status, stat.ptr)
+        if status.any():
+            if (status == 1).any():
+                raise ValueError("cannot encode inf / nan")
+            return None
+        if kind == 2:
+            e32 = np.empty(count, dtype=np.int32)
+            self.ctx.d2h(e32, e_dev.ptr)
+            exps[:] = e32
+        return out, exps
+
+    def values_decode_dev(self, plain, kind, exps=None):
+        """resident plaintext rows -> (uint64 words: int64 values for kind 0, float64 values for kind 1 — view them —, uint8
+        status per row) on the host.  exps: the rows' exponents (kind 1).  Status 1: the overflow gap, 2: beyond 64 bits (or
+        int64), 3: m >= n; the word of such a row means nothing."""
+        rows = plain.rows
+        out, status = np.empty(rows, dtype=np.uint64), np.empty(rows, dtype=np.uint8)
+        if rows:
+            if plain.cols != self.n_limbs:
+                raise ValueError("the rows have %d words" % plain.cols)
+            e_dev = DeviceArray.from_host(self.ctx, np.ascontiguousarray(exps, dtype=np.int32).view(np.uint32)) if kind == 1 else None
+            if e_dev is not None and e_dev.rows != rows:
+                raise ValueError("%d exponents for %d rows" % (e_dev.rows, rows))
+            v, s = DeviceArray(self.ctx, rows, 2), DeviceArray(self.ctx, (rows + 3) // 4, 1)
+            self.ctx.values_decode_dev(plain.ptr, rows, kind, e_dev.ptr if e_dev else None, v.ptr, s.ptr)
+            self.ctx.sync()
+            self.ctx.d2h(out, v.ptr)
+            self.ctx.d2h(status, s.ptr)
+        return out, status
+
+    def raw_decrypt_decode_chunks(self, c, kind, exps=None, chunk=1 << 16):
+        """raw_decrypt + decoding as a generator of (lo, hi, uint64 words of rows [lo, hi), status bytes, fetch): the twin of
+        raw_decrypt_unpack_chunks with the decode kernel queued behind each chunk's decrypt on the same stream, so that 8 bytes
+        and a status byte per row come down instead of limb rows.  kind 0: int64 words, kind 1: float64 words at the exponents
+        `exps` (one per row of c, each in [-240, 0)).  fetch(indices) downloads the plaintext rows of the chunk at those indices
+        (relative to lo) as host limbs — for the rows whose status says that the host must decode them; it is valid until the
+        generator is advanced.  c: a resident vector (DeviceArray) or host limb rows.  The engine's lock is taken around each
+        step, never across a yield."""
+        with self._lock:
+            st = self._launch_stream()
+        resident = isinstance(c, DeviceArray)
+        rows = c.rows if resident else c.shape[0]
+        if rows == 0:
+            return
+        e32 = np.ascontiguousarray(exps, dtype=np.int32) if kind == 1 else None
+        bounds = [(lo, min(rows, lo + chunk)) for lo in range(0, rows, chunk)]
+        staged, running = {}, {}
+
+        def stage(k):
+            lo, hi = bounds[k]
+            staged[k] = (c.rows_view(lo, hi) if resident else DeviceArray.from_host(self.ctx, c[lo:hi]),
+                         DeviceArray(self.ctx, hi - lo, self.n_limbs), DeviceArray(self.ctx, hi - lo, 2),
+                         DeviceArray(self.ctx, (hi - lo + 3) // 4, 1),
+                         DeviceArray.from_host(self.ctx, e32[lo:hi].view(np.uint32)) if kind == 1 else None)
+
+        def launch(k):
+            lo, hi = bounds[k]
+            src, plain, vals, stat, e_dev = running[k] = staged.pop(k)
+            self.ctx.decrypt_dev(src.ptr, plain.ptr, hi - lo, st)
+            self.ctx.values_decode_dev(plain.ptr, hi - lo, kind, e_dev.ptr if e_dev else None, vals.ptr, stat.ptr, st)
+        try:
+            with self._lock:
+                stage(0)
+                launch(0)
+            for k, (lo, hi) in enumerate(bounds):
+                with self._lock:
+                    if k + 1 < len(bounds):
+                        stage(k + 1)                             # upload under the kernels of chunk k
+                    self.ctx.sync(st)                            # chunk k is complete
+                    if k + 1 < len(bounds):
+                        launch(k + 1)
+                    _, plain, vals, stat, _ = running.pop(k)
+                    values, status = np.empty(hi - lo, dtype=np.uint64), np.empty(hi - lo, dtype=np.uint8)
+                    self.ctx.d2h(values, vals.ptr)               # blocking copies on the NULL stream, under chunk k+1
+                    self.ctx.d2h(status, stat.ptr)
+                    del vals, stat
+
+                def fetch(indices, plain=plain):
+                    with self._lock:
+                        idx = DeviceArray.from_host(self.ctx, np.ascontiguousarray(indices, dtype=np.uint32))
+                        sub = DeviceArray(self.ctx, idx.rows, self.n_limbs)
+                        self.ctx.gather_rows_dev(plain.ptr, plain.rows, idx.ptr, sub.ptr, self.n_limbs, idx.rows)
+                        self.ctx.sync()
+                        return sub.to_host()
+                yield lo, hi, values, status, fetch
+                del fetch, plain
+        finally:
+            # a consumer that stops early (an overflow row) drops the generator with the next chunk's kernels still writing:
+            # wait for them before the blocks return to the size-keyed pool
+            self.ctx.sync(st)
+            running.clear()
+            staged.clear()
+
     def obfuscate_fresh_dev(self, c, rows=None):
         """obfuscate_dev with freshly drawn obfuscators, chunked like raw_encrypt_fresh (draw and upload of the next
         chunk under the kernels of the current one).  rows: indices that get a fresh r (None = all); the others get

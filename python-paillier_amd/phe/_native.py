@@ -18,7 +18,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("PHE_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libphe_hip.so")
 
 OK, EINVAL, EHIP, ENOINVERSE = 0, 1, 2, 3
-ABI_VERSION = 13         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
+ABI_VERSION = 14         # include/phe_hip.h PHE_HIP_ABI_VERSION as mirrored below (tests/test_abi_exports.py compares the two)
 
 _lib = None
 
@@ -119,6 +119,8 @@ def lib():
         L.phe_hip_segment_plan_level_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, sz, vp]
         L.phe_hip_slots_pack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
         L.phe_hip_slots_unpack_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+        L.phe_hip_values_encode_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_int32, vp, vp, vp, vp]
+        L.phe_hip_values_decode_dev.argtypes = [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp]
         L.phe_hip_fixed_base_set.argtypes = [vp, vp, ci, ci]
         L.phe_hip_fixed_base_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(sz)]
         L.phe_hip_fixed_base_clear.argtypes = [vp]
@@ -148,6 +150,7 @@ EXPORTED_SYMBOLS = [
     "phe_hip_pair_words", "phe_hip_to_pair_dev", "phe_hip_pair_mul_dev", "phe_hip_from_pair_dev", "phe_hip_pair_reduce_dev",
     "phe_hip_pair_powmod_dev", "phe_hip_pair_multiexp_rows_dev", "phe_hip_segment_reduce_dev",
     "phe_hip_segment_scan_dev", "phe_hip_segment_pack_dev", "phe_hip_slots_pack_dev", "phe_hip_slots_unpack_dev",
+    "phe_hip_values_encode_dev", "phe_hip_values_decode_dev",
     "phe_hip_fixed_base_set", "phe_hip_fixed_base_info", "phe_hip_fixed_base_clear", "phe_hip_fixed_base_rows_dev",
     "phe_hip_fixed_base_pow_dev", "phe_hip_chacha20_rows_dev", "phe_hip_segment_plan_sort_dev", "phe_hip_segment_plan_level_dev",
 ]
@@ -457,6 +460,14 @@ class Context:
     def slots_unpack_dev(self, m_ptr, rows, slots, slot_bits, values_ptr, status_ptr, stream=0):
         """int64 slots and one status byte per plaintext row (include/phe_hip.h phe_hip_slots_unpack_dev)"""
         _check(lib().phe_hip_slots_unpack_dev(self._h, m_ptr, rows, slots, slot_bits, values_ptr, status_ptr, stream))
+
+    def values_encode_dev(self, bits_ptr, count, kind, exponent, m_ptr, exps_ptr, status_ptr, stream=0):
+        """plaintext rows, exponents and one status byte per 64-bit value word (include/phe_hip.h phe_hip_values_encode_dev)"""
+        _check(lib().phe_hip_values_encode_dev(self._h, bits_ptr, count, kind, exponent, m_ptr, exps_ptr, status_ptr, stream))
+
+    def values_decode_dev(self, m_ptr, rows, kind, exps_ptr, out_ptr, status_ptr, stream=0):
+        """one int64 / float64 word and one status byte per plaintext row (include/phe_hip.h phe_hip_values_decode_dev)"""
+        _check(lib().phe_hip_values_decode_dev(self._h, m_ptr, rows, kind, exps_ptr, out_ptr, status_ptr, stream))
 
     # ---- host-array entry points (numpy uint32, row-major (batch, limbs)) ----
     def encrypt(self, m, r):

@@ -30,6 +30,10 @@ SCALAR_POOL_REFILL = 4096
 # decrypt_packed returning a LIST also goes through the unpack kernel where it can (False: lists are unpacked on the host, only
 # as_array=True takes the kernel)
 PACKED_LISTS_THROUGH_CODEC = True
+# encrypt_batch forms the plaintext rows of int64 / uint64 / float64 arrays on the GPU (Engine.values_encode_dev) from this many
+# values on; below it the host encoding stays (same bits either way).  The crossover is measured by tools/bench_value_codec.py
+# (profiles/r15_value_codec.json)
+VALUE_CODEC_DEVICE_MIN = 2048
 
 
 def _gpu_prime_search_available():
@@ -376,23 +380,49 @@ class PaillierPublicKey(object):
     def encrypt_batch(self, values, precision=None, r_values=None, device=False, rho_values=None):
         """Encode + encrypt a whole sequence / numpy array -> EncryptedVector (one kernel launch).
         device=True keeps the ciphertexts resident in HBM for later homomorphic operations.
-        float64 / integer numpy arrays are encoded and drawn without a Python integer per element.
+        float64 / integer numpy arrays are encoded and drawn without a Python integer per element; from
+        VALUE_CODEC_DEVICE_MIN values on, int64 / uint64 / float64 arrays (float64 also under a `precision`: one common
+        exponent, mantissas rounded half to even) are encoded on the GPU and only their 8 bytes per value are uploaded
+        (Engine.values_encode_dev: same bits, exponents and exceptions as the host encoding).
         rho_values (with enable_short_obfuscators): the exponents of the obfuscators h_s^rho given explicitly, as integers in
         [0, 2^bits) or (count, ceil(bits / 32)) uint32 rows — row i is raw_encrypt(m_i, r_value=pow(h, rho_i, n))."""
         from .ciphertext import EncryptedVector
+        from ._device import DeviceArray
         eng = self._get_engine()
         fresh = r_values is None and rho_values is None
-        signed = EncodedNumber.encode_signed(values, precision) if eng.n_limbs >= 4 else None
-        if signed is not None:
-            mag, neg, exps = signed
-            m = EncodedNumber.signed_to_limbs(self, mag, neg, eng.n_limbs)
-        else:
-            m, exps = EncodedNumber.encode_many(self, values, precision)
+        m = exps = None
+        arr = self._value_codec_array(eng, values, precision, device)
+        if arr is not None:
+            # the rows are formed where they are used (Engine.values_encode_dev): 8 bytes per value go up, the exponents and a
+            # status byte come down; this happens — and raises — before any pool obfuscator is taken
+            if precision is None:
+                got = eng.values_encode_dev(arr)
+            else:
+                try:
+                    got = eng.values_encode_dev(arr, EncodedNumber._natural_exponent(0.0, precision))
+                except ValueError:
+                    got = None                                     # inf / nan under a precision: the host route's own exceptions
+            if got is not None:
+                m, exps = got
+                if precision is not None:
+                    exps = np.full(len(arr), exps, dtype=np.int64)
+        if m is None:
+            signed = EncodedNumber.encode_signed(values, precision) if eng.n_limbs >= 4 else None
+            if signed is not None:
+                mag, neg, exps = signed
+                m = EncodedNumber.signed_to_limbs(self, mag, neg, eng.n_limbs)
+            else:
+                m, exps = EncodedNumber.encode_many(self, values, precision)
+        resident = isinstance(m, DeviceArray)
         count = len(exps)
         limbs = None
         if rho_values is not None:
             rho = self._rho_limbs(rho_values, count, r_values)
-            limbs = eng.short_pow_dev(rho, m=m) if device else eng.short_pow(rho, m=m)
+            if resident:
+                limbs = eng.short_pow_dev(rho, m=m)
+                limbs = limbs if device else limbs.to_host()
+            else:
+                limbs = eng.short_pow_dev(rho, m=m) if device else eng.short_pow(rho, m=m)
             return EncryptedVector(self, limbs, exps, obfuscated=False)
         fl = self._get_fleet() if (not device and isinstance(m, np.ndarray)) else None
         if fl is not None and len(fl.shards(count)) > 1:
@@ -410,7 +440,7 @@ class PaillierPublicKey(object):
                 r_all = r_values if isinstance(r_values, np.ndarray) else eng.plain_limbs(list(r_values))
                 shard = lambda e, lo, hi: e.raw_encrypt(m[lo:hi], r_all[lo:hi])
             return EncryptedVector(self, np.concatenate(fl.run(count, shard)), exps, obfuscated=fresh)
-        if fresh and isinstance(m, np.ndarray) and hasattr(eng.ctx, "encrypt_dev"):
+        if fresh and isinstance(m, (np.ndarray, DeviceArray)) and hasattr(eng.ctx, "encrypt_dev"):
             # online part only: (1 + n m) * r^n with r^n from the pool made by precompute_obfuscators (each used once)
             limbs = eng.encrypt_from_obfuscators(m)
             if limbs is None and 0 < count <= SCALAR_POOL_REFILL // 4:
@@ -419,15 +449,50 @@ class PaillierPublicKey(object):
         if limbs is not None:
             if not device:
                 limbs = limbs.to_host()
-        elif fresh and isinstance(m, np.ndarray) and hasattr(eng.ctx, "encrypt_dev"):
+        elif fresh and isinstance(m, (np.ndarray, DeviceArray)) and hasattr(eng.ctx, "encrypt_dev"):
             limbs = eng.raw_encrypt_fresh(m, device)
-        elif fresh and self._short is not None:
+        elif fresh and self._short is not None and not resident:
             rho = self._draw_rho(eng, count)
             limbs = eng.short_pow_dev(rho, m=m) if device else eng.short_pow(rho, m=m)
         else:
             r = random_lt_n_limbs(self.n, count, eng.n_limbs) if fresh else list(r_values)
-            limbs = eng.raw_encrypt_dev(m, r) if device else eng.raw_encrypt(m, r)
+            if resident and not device:
+                if len(r) != count:
+                    raise ValueError("m and r batch sizes differ")
+                limbs = eng.raw_encrypt_dev(m, r).to_host()        # resident rows in, the ciphertexts come down
+            else:
+                limbs = eng.raw_encrypt_dev(m, r) if device else eng.raw_encrypt(m, r)
         return EncryptedVector(self, limbs, exps, obfuscated=fresh)
+
+    def _value_codec_array(self, eng, values, precision, device):
+        """the array encrypt_batch hands to the device codec (Engine.values_encode_dev) — int64, uint64 or float64, flat — or
+        None where the host encoding stays: other element types (lists become arrays by the rules of
+        EncodedNumber.encode_signed), integers with a precision, another BASE than 16, a key with max_int < 2^64, a backend
+        without the kernels, a batch below VALUE_CODEC_DEVICE_MIN, or a host batch that the fleet fans out."""
+        if EncodedNumber.BASE != 16 or EncodedNumber.FLOAT_MANTISSA_BITS != 53 or not eng.has_value_codec():
+            return None
+        if isinstance(values, (list, tuple)) and len(values) >= max(1, VALUE_CODEC_DEVICE_MIN):
+            kind = type(values[0])
+            if kind is float and all(type(v) is float for v in values):
+                values = np.array(values, dtype=np.float64)
+            elif kind is int and precision is None and all(type(v) is int for v in values):
+                try:
+                    values = np.array(values, dtype=np.int64)
+                except OverflowError:
+                    return None
+        if not isinstance(values, np.ndarray) or values.size < max(1, VALUE_CODEC_DEVICE_MIN):
+            return None
+        if values.dtype == np.float64:
+            arr = values.reshape(-1)
+        elif values.dtype.kind in "iu" and precision is None:
+            arr = values.reshape(-1).astype(np.uint64 if values.dtype.kind == "u" else np.int64, copy=False)
+        else:
+            return None
+        if not device:
+            fl = self._get_fleet()
+            if fl is not None and len(fl.shards(len(arr))) > 1:
+                return None
+        return arr
 
     def _packed_mantissas(self, values, precision):
         """(signed mantissas, exponent) of encrypt_packed: element-wise the int_rep and exponent that
@@ -758,8 +823,17 @@ class PaillierPrivateKey(object):
         # ciphertexts are residues mod n^2; reduce stray larger ints exactly like powmod would
         return eng.to_ints(eng.raw_decrypt([c % self.public_key.nsquare for c in ciphertexts]))
 
-    def decrypt_batch(self, vector, Encoding=None):
-        """EncryptedVector (or list of EncryptedNumber) -> list of decoded ints/floats."""
+    def decrypt_batch(self, vector, Encoding=None, as_array=False):
+        """EncryptedVector (or list of EncryptedNumber) -> list of decoded ints/floats.
+        as_array=True returns a numpy array instead — np.int64 when every exponent is 0, np.float64 when every exponent is
+        negative — and raises ValueError where that form does not apply: a custom Encoding, exponents of both kinds or positive
+        ones.  The values are those of the list; a row in the overflow gap raises OverflowError('Overflow detected in decrypted
+        number'), an integer outside int64 OverflowError, a plaintext >= n the corrupted-number ValueError, and the lowest row
+        index decides which.  With the value codec kernels (Engine.has_value_codec) and exponents of -240 or more the decode
+        kernel runs behind each chunk's decrypt (Engine.raw_decrypt_decode_chunks): 8 bytes and a status byte per row come
+        down instead of limb rows."""
+        if as_array:
+            return self._decrypt_batch_array(vector, Encoding)
         from .ciphertext import EncryptedVector
         if isinstance(vector, (list, tuple)) and vector and all(isinstance(v, EncryptedVector) for v in vector):
             # the per-device list of encrypt_batch_sharded: every part on the engine of its own device, concurrently
@@ -804,6 +878,79 @@ class PaillierPrivateKey(object):
         if plain_decode:
             return EncodedNumber.decode_limbs(self.public_key, plain, vector.exponent_array)
         return Encoding.decode_many(self.public_key, eng.to_ints(plain), vector.exponents)
+
+    def _decrypt_batch_array(self, vector, Encoding):
+        """decrypt_batch(as_array=True)"""
+        from .ciphertext import EncryptedVector
+        if isinstance(vector, (list, tuple)) and vector and all(isinstance(v, EncryptedVector) for v in vector):
+            # the per-device list of encrypt_batch_sharded, part after part: the lowest row decides which exception is raised
+            parts = [self._decrypt_batch_array(v, Encoding) for v in vector]
+            kinds = {part.dtype for part, v in zip(parts, vector) if len(v)}
+            if len(kinds) > 1:
+                raise ValueError("as_array needs exponents that are all 0 (int64) or all negative (float64)")
+            dtype = kinds.pop() if kinds else np.dtype(np.int64)
+            return np.concatenate([part.astype(dtype, copy=False) for part in parts])
+        if not isinstance(vector, EncryptedVector):
+            vector = EncryptedVector.from_numbers(self.public_key, vector)
+        if self.public_key != vector.public_key:
+            raise ValueError('encrypted_number was encrypted against a different key!')
+        if not (Encoding is None or Encoding is EncodedNumber):
+            raise ValueError("as_array does not apply to a custom Encoding")
+        pk = self.public_key
+        exps = vector.exponent_array
+        all_int, all_float = bool((exps == 0).all()), bool(len(exps) and (exps < 0).all())
+        if not (all_int or all_float):
+            raise ValueError("as_array needs exponents that are all 0 (int64) or all negative (float64)")
+        dtype = np.int64 if all_int else np.float64
+        if len(vector) == 0:
+            return np.zeros(0, dtype=dtype)
+        eng = self._get_engine()
+        fl = self._get_fleet()
+        if vector.on_device and fl is not None:
+            eng = self.public_key._engine_for(vector._store)
+        fanned_out = not vector.on_device and fl is not None and len(fl.shards(len(vector))) > 1
+        parts = []
+        if EncodedNumber.BASE == 16 and int(exps.min()) >= -240 and not fanned_out and eng.has_value_codec():
+            kind = 0 if all_int else 1
+            chunks = eng.raw_decrypt_decode_chunks(vector.limbs(be_secure=False), kind, exps if kind else None)
+            for lo, hi, words, status, fetch in chunks:
+                bad = np.flatnonzero(status)
+                if len(bad):
+                    # in row order: the rows the host must decode (status 2 of the float kind) up to the first row that raises
+                    stop = next((int(i) for i in bad if not (kind == 1 and status[i] == 2)), None)
+                    redo = [int(i) for i in bad if stop is None or i < stop]
+                    if redo:
+                        plain = eng.to_ints(fetch(redo))
+                        vals = words.view(np.float64)
+                        for i, m in zip(redo, plain):
+                            vals[i] = EncodedNumber(pk, m, int(exps[lo + i])).decode()
+                    if stop is not None:
+                        if status[stop] == 1:
+                            raise OverflowError('Overflow detected in decrypted number')
+                        if status[stop] == 3:
+                            raise ValueError('Attempted to decode corrupted number')
+                        raise OverflowError('the integer at index %d does not fit int64' % (lo + stop))
+                parts.append(words.view(dtype))
+            return parts[0] if len(parts) == 1 else np.concatenate(parts)
+        # the list route, chunk by chunk, into the same array
+        for lo, hi, plain in self._raw_plain_chunks(vector):
+            try:
+                vals = EncodedNumber.decode_limbs(pk, plain, exps[lo:hi])
+                failed = False
+            except (OverflowError, ValueError):
+                failed = True
+            if failed:                                                 # row by row: the lowest row decides what is raised
+                vals = []
+                for m, e in zip(eng.to_ints(plain), exps[lo:hi].tolist()):
+                    vals.append(EncodedNumber(pk, m, e).decode())
+                    if all_int and not -(1 << 63) <= vals[-1] < 1 << 63:
+                        raise OverflowError('the integer at index %d does not fit int64' % (lo + len(vals) - 1))
+            try:
+                parts.append(np.asarray(vals, dtype=dtype))
+            except OverflowError:
+                i = next(i for i, v in enumerate(vals) if not -(1 << 63) <= v < 1 << 63)
+                raise OverflowError('the integer at index %d does not fit int64' % (lo + i)) from None
+        return parts[0] if len(parts) == 1 else np.concatenate(parts)
 
     def _raw_plain_chunks(self, vector):
         """(lo, hi, plaintext limb rows on the host) over an EncryptedVector, by the raw decrypt paths of decrypt_batch:
