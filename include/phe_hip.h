@@ -301,6 +301,20 @@ int phe_hip_segment_scan_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_ar
  * plaintext space.  EINVAL without the split-modulus engine. */
 int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_are_pair, size_t n_rows, uint32_t slots,
                              uint32_t slot_bits, uint32_t* out_pair, size_t tasks, void* stream);
+/* Simultaneous inversion on resident rows: pair_out[i] = pair_in[i]^-1 mod n^2, pair rows in and out — invert(c, n^2) of the
+ * negative-scalar branch of EncryptedNumber.__mul__ / _raw_mul (phe/paillier.py:745-749), hence of __neg__ and __sub__, without
+ * leaving the form.  Montgomery's trick on blocks of block_rows consecutive rows, one block per limb group
+ * (csrc/pair_invert.h): down the levels the running products of every block and the blocks' totals, which are the rows of the
+ * next level, until one row is left; that root leaves the form, is inverted on the host and enters it again; up the levels
+ * every block walks back from the inverse of its total.  3 pair products per row and level, rows * (1 + 1/(block_rows - 1))
+ * rows over all levels, two launches per level; phe_hip_invert_dev pays 3 full-width products per row and 2 log2(rows)
+ * launches.  block_rows == 0: the library's default (4); 1: EINVAL.  pair_out must not be pair_in (EINVAL); at most 2^32 - 1
+ * rows.  The running products and the upper levels live in a buffer of the context that grows on demand
+ * (phe_hip_ctx_release_scratch frees it).  On PHE_HIP_ENOINVERSE *bad_index is the first row that is not a unit: the code and
+ * the index phe_hip_invert_dev gives for the same residues.  Synchronises `stream` internally like phe_hip_invert_dev (the
+ * root makes one round trip to the host); results are complete on return.  EINVAL without the split-modulus engine. */
+int phe_hip_pair_invert_dev(phe_hip_ctx* ctx, const uint32_t* pair_in, uint32_t* pair_out, size_t batch, uint32_t block_rows,
+                            size_t* bad_index, void* stream);
 /* The slot codec of packed plaintexts (csrc/slot_codec.h): S = slots signed values of B = slot_bits bits (1 <= B <= 64,
  * S*B <= max_int.bit_length() - 1) per plaintext row, the conventions of EncryptedVector.pack / decrypt_packed.  Both kernels
  * move bit fields and are bound by memory.

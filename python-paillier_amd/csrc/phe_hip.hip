@@ -31,6 +31,7 @@
 #include "mont_core.h"
 #include "split_core.h"
 #include "segment_core.h"
+#include "pair_invert.h"
 #include "slot_codec.h"
 #include "value_codec.h"
 #include "fixed_base.h"
@@ -131,6 +132,9 @@ int launch_segment_reduce(int G, int L, int blocks, hipStream_t st, const Segmen
 int launch_segment_scan(int G, int L, int blocks, hipStream_t st, const ScanArgs& A);
 int launch_segment_pack(int G, int L, int blocks, hipStream_t st, const PackArgs& A);
 }  // namespace seg
+namespace inv {  // kernels_inv.hip
+int launch_pair_invert(int G, int L, bool up, int blocks, hipStream_t st, const PairInvertArgs& A);
+}  // namespace inv
 namespace slots {  // kernels_slots.hip
 int launch_slots_pack(int G, int K, int blocks, hipStream_t st, const SlotPackArgs& A);
 int launch_slots_unpack(int G, int K, int blocks, hipStream_t st, const SlotUnpackArgs& A);
@@ -467,6 +471,8 @@ struct phe_hip_ctx {
     size_t item_sched_words = 0;
     uint32_t* partial = nullptr;  // multi-exponentiation: one product per chunk, joined in place by a k_mulmod tree
     size_t partial_words = 0;
+    uint32_t* inv_tree = nullptr;  // simultaneous inversion on pair rows: the running products and the upper levels
+    size_t inv_tree_words = 0;
     // encryption by the key owner (CRT lift): K*R, (q^2 - K)*R mod q^2 and p^2 as rows of d_qsq.S limbs; null = not offered
     uint32_t* owner_blob = nullptr;
     int owner_G = 0, owner_L = 0;
@@ -1501,7 +1507,7 @@ void phe_hip_ctx_destroy(phe_hip_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     std::vector<uint32_t*> bufs = {ctx->d_nsplit.blob, ctx->d_psplit.blob, ctx->d_qsplit.blob,
                         ctx->d_nsq.blob, ctx->d_psq.blob, ctx->d_qsq.blob, ctx->d_exp_n.ops, ctx->d_exp_p.ops,
-                        ctx->d_exp_q.ops, ctx->d_tail.blob, ctx->table, ctx->table2, ctx->scratch, ctx->partial, ctx->lookup, (uint32_t*)ctx->flags, ctx->stage[0],
+                        ctx->d_exp_q.ops, ctx->d_tail.blob, ctx->table, ctx->table2, ctx->scratch, ctx->partial, ctx->inv_tree, ctx->lookup, (uint32_t*)ctx->flags, ctx->stage[0],
                         ctx->stage[1], ctx->stage[2], ctx->owner_blob, ctx->d_nunit.blob, ctx->unit_tmp, ctx->tail_wave_blob, ctx->item_sched,
                         ctx->tmul_blob, ctx->tmul_cols, ctx->fb_table};
     for (const auto& R : ctx->pub_rungs) { bufs.push_back(R.nsq.blob); bufs.push_back(R.nsplit.blob); bufs.push_back(R.nunit.blob); }
@@ -2206,6 +2212,95 @@ int phe_hip_segment_pack_dev(phe_hip_ctx* ctx, const uint32_t* rows, int rows_ar
     if (phe::seg::launch_segment_pack(sp.G, sp.L, blocks, (hipStream_t)stream, A) < 0)
         return fail(PHE_HIP_EINVAL, "unsupported split geometry");
     HIP_TRY(hipGetLastError());
+    return PHE_HIP_OK;
+}
+
+// ---- simultaneous inversion on pair rows (pair_invert.h, kernels_inv.hip) -------------------------------------------------------
+// out[i] = pair_in[i]^-1 mod n^2, both in the pair form: invert(c, n^2) of the negative-scalar branch of _raw_mul
+// (phe/paillier.py:745-749) without leaving the form.  Down the levels the running products of every block of rows and the
+// blocks' totals (one launch per level), the root out of the form, inverted on the host and back into it, then up the levels
+// the inverses (one launch per level): 3 pair products per row and level.  The context's inv_tree holds
+//     P_0 (batch rows) | per upper level k: X_k, P_k, Inv_k (rows[k] each) | the root and its inverse as 32-bit words.
+constexpr uint32_t kPairInvertBlockRows = 4;   // block_rows == 0 (phe/_engine.py PAIR_INVERT_BLOCK_ROWS is the same figure)
+
+static bool host_invert(const Big& a_in, const Big& N, Big& out);
+static int first_non_unit(phe_hip_ctx* ctx, const uint32_t* words_dev, size_t batch, size_t* bad_index);
+
+int phe_hip_pair_invert_dev(phe_hip_ctx* ctx, const uint32_t* pair_in, uint32_t* pair_out, size_t batch, uint32_t block_rows,
+                            size_t* bad_index, void* stream) {
+    if (check_ctx(ctx)) return PHE_HIP_EINVAL;
+    if (block_rows == 1) return fail(PHE_HIP_EINVAL, "a block of one row makes no level shorter than the one below");
+    if (batch == 0) return PHE_HIP_OK;
+    if (!pair_in || !pair_out) return fail(PHE_HIP_EINVAL, "null buffer");
+    if (pair_in == pair_out) return fail(PHE_HIP_EINVAL, "pair_out must not be pair_in");
+    if (batch > 0xFFFFFFFFull) return fail(PHE_HIP_EINVAL, "row numbers are 32-bit");
+    if (int rc = bind_device(ctx)) return rc;
+    if (!(ctx->use_split && ctx->d_nsplit.G)) return fail(PHE_HIP_EINVAL, "the pair form needs the split-modulus engine");
+    PHE_CTX_ORDER(ctx, stream);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t w = (size_t)2 * ctx->d_nsplit.H, s2 = (size_t)ctx->pub.s2;
+    const phe::InvertLevels lv = phe::invert_levels(batch, block_rows ? block_rows : kPairInvertBlockRows);
+    const size_t top = lv.rows.size() - 1;  // the level of one row: the root
+    if (int rc = ensure_words(&ctx->inv_tree, &ctx->inv_tree_words, (batch + 3 * (size_t)lv.upper_rows) * w + 2 * s2)) return rc;
+    // where level k's input, running products and inverses live
+    std::vector<const uint32_t*> X(top + 1);
+    std::vector<uint32_t*> P(top + 1), I(top + 1);
+    uint32_t* cursor = ctx->inv_tree;
+    X[0] = pair_in;
+    P[0] = cursor;
+    I[0] = pair_out;
+    cursor += batch * w;
+    for (size_t k = 1; k <= top; ++k) {
+        X[k] = cursor;
+        P[k] = cursor + lv.rows[k] * w;
+        I[k] = cursor + 2 * lv.rows[k] * w;
+        cursor += 3 * lv.rows[k] * w;
+    }
+    uint32_t* root_words = cursor;
+    uint32_t* rinv_words = cursor + s2;
+    int geom0 = 0;
+    auto walk = [&](size_t k, bool up) -> int {
+        const DevSplit& sp = pick_pair_split(ctx, (size_t)lv.rows[k + 1]);
+        PairInvertArgs A;
+        A.mod = sp.c;
+        A.x = X[k];
+        A.prefix = P[k];
+        A.totals = const_cast<uint32_t*>(X[k + 1]);
+        A.inv = I[k + 1];
+        A.out = I[k];
+        A.n_rows = lv.rows[k];
+        A.block_rows = lv.block[k];
+        A.blocks = lv.rows[k + 1];
+        if (k == 0) geom0 = geom_code(sp.G, sp.L);
+        const int blocks = grid_blocks(ctx, (size_t)A.blocks, sp.G, 2);
+        if (phe::inv::launch_pair_invert(sp.G, sp.L, up, blocks, st, A) < 0) return fail(PHE_HIP_EINVAL, "unsupported split geometry");
+        HIP_TRY(hipGetLastError());
+        return PHE_HIP_OK;
+    };
+    for (size_t k = 0; k < top; ++k)
+        if (int rc = walk(k, false)) return rc;
+    // the root: out of the form, one scalar inversion on the host, back into the form
+    if (int rc = pair_launch(ctx, 1, X[top], nullptr, 0, ctx->pub.s1, root_words, 1, st)) return rc;
+    Big root(s2), N = ctx->pub.nsq32, rinv;
+    HIP_TRY(hipMemcpyAsync(root.data(), root_words, s2 * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!host_invert(root, N, rinv)) {
+        // slow path only on failure: the rows out of the form, the first of them that is not a unit
+        if (int rc = ensure_words(&ctx->stage[0], &ctx->stage_words[0], batch * s2)) return rc;
+        if (int rc = pair_launch(ctx, 1, pair_in, nullptr, 0, ctx->pub.s1, ctx->stage[0], batch, st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        return first_non_unit(ctx, ctx->stage[0], batch, bad_index);
+    }
+    rinv.resize(s2, 0u);
+    HIP_TRY(hipMemcpyAsync(rinv_words, rinv.data(), s2 * 4, hipMemcpyHostToDevice, st));
+    if (int rc = pair_launch(ctx, 0, rinv_words, nullptr, 0, 0, I[top], 1, st)) return rc;
+    for (size_t k = top; k-- > 0;)
+        if (int rc = walk(k, true)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));  // rinv (host) was an async source; results are complete on return
+    if (top) {
+        ctx->last_path = 0;
+        ctx->last_geom_pub = geom0;  // (phe_hip_ctx_last_launch: the geometry of the rows' own level, not of the root's conversion)
+    }
     return PHE_HIP_OK;
 }
 
@@ -2977,10 +3072,11 @@ int phe_hip_ctx_release_scratch(phe_hip_ctx* ctx) {
     if (int rc = bind_device(ctx)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     uint32_t** bufs[] = {&ctx->table, &ctx->table2, &ctx->scratch, &ctx->partial, &ctx->lookup, &ctx->unit_tmp,
-                         &ctx->stage[0], &ctx->stage[1], &ctx->stage[2], &ctx->item_sched};
+                         &ctx->stage[0], &ctx->stage[1], &ctx->stage[2], &ctx->item_sched, &ctx->inv_tree};
     size_t* sizes[] = {&ctx->table_words, &ctx->table2_words, &ctx->scratch_words, &ctx->partial_words, &ctx->lookup_words,
-                       &ctx->unit_tmp_words, &ctx->stage_words[0], &ctx->stage_words[1], &ctx->stage_words[2], &ctx->item_sched_words};
-    for (int i = 0; i < 10; ++i) {
+                       &ctx->unit_tmp_words, &ctx->stage_words[0], &ctx->stage_words[1], &ctx->stage_words[2], &ctx->item_sched_words,
+                       &ctx->inv_tree_words};
+    for (int i = 0; i < 11; ++i) {
         if (*bufs[i]) HIP_TRY(hipFree(*bufs[i]));
         *bufs[i] = nullptr;
         *sizes[i] = 0;
@@ -3200,6 +3296,23 @@ int phe_hip_multiexp(phe_hip_ctx* ctx, const uint32_t* base, const uint32_t* e, 
 // ---- batched inversion (Montgomery's trick over a product tree) ------------------------------------
 static bool host_invert(const Big& a_in, const Big& N, Big& out) { return host::big_invert_odd(a_in, N, out); }
 
+// the failure path of both inversions: the first of `batch` device rows of 32-bit words that has no inverse modulo n^2
+static int first_non_unit(phe_hip_ctx* ctx, const uint32_t* words_dev, size_t batch, size_t* bad_index) {
+    const size_t w = (size_t)ctx->pub.s2;
+    const Big N = ctx->pub.nsq32;
+    std::vector<uint32_t> h(batch * w);
+    HIP_TRY(hipMemcpy(h.data(), words_dev, batch * w * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < batch; ++i) {
+        Big x(h.begin() + (long)(i * w), h.begin() + (long)((i + 1) * w)), tmp;
+        Big xr = host::big_cmp(x, N) < 0 ? x : host::big_mod(x, N);
+        if (!host_invert(xr, N, tmp)) {
+            if (bad_index) *bad_index = i;
+            return fail(PHE_HIP_ENOINVERSE, "invert() no inverse exists");
+        }
+    }
+    return fail(PHE_HIP_EINVAL, "inversion failed although every element is a unit (operands must be < n^2)");
+}
+
 // a_is_device/out_is_device pick the copy kinds; the trees live in stage[0] (products) and stage[1] (inverses).
 static int invert_impl(phe_hip_ctx* ctx, const uint32_t* a, bool a_is_device, uint32_t* out, bool out_is_device,
                        size_t batch, size_t* bad_index, hipStream_t st) {
@@ -3235,17 +3348,7 @@ static int invert_impl(phe_hip_ctx* ctx, const uint32_t* a, bool a_is_device, ui
     const bool reduced_ok = host::big_cmp(root, N) < 0;
     if (!reduced_ok || !host_invert(root, N, rinv)) {
         // slow path only on failure: find the first row that is not a unit (or not reduced)
-        std::vector<uint32_t> h(batch * w);
-        HIP_TRY(hipMemcpy(h.data(), prod, batch * w * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < batch; ++i) {
-            Big x(h.begin() + (long)(i * w), h.begin() + (long)((i + 1) * w)), tmp;
-            Big xr = host::big_cmp(x, N) < 0 ? x : host::big_mod(x, N);
-            if (!host_invert(xr, N, tmp)) {
-                if (bad_index) *bad_index = i;
-                return fail(PHE_HIP_ENOINVERSE, "invert() no inverse exists");
-            }
-        }
-        return fail(PHE_HIP_EINVAL, "inversion failed although every element is a unit (operands must be < n^2)");
+        return first_non_unit(ctx, prod, batch, bad_index);
     }
     HIP_TRY(hipMemcpyAsync(inv + off.back() * w, rinv.data(), w * 4, hipMemcpyHostToDevice, st));
     for (size_t k = cnt.size() - 1; k-- > 0;) {

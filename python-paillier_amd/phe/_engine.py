@@ -309,6 +309,21 @@ def plan_segments(seg_ids, n_segments, cap=None):
 SCAN_TASK_ROWS = 16
 SCAN_NO_CARRY = 0xFFFFFFFF
 
+# ---- inversion on pair rows (Engine.pair_invert_dev; csrc/pair_invert.h) ---------------------------------------------------------
+# One limb group walks a block of this many consecutive rows, once down (running products) and once up (inverses); the blocks'
+# totals are the rows of the next level.  Short blocks fill the GPU and keep the dependent chain of a walk short; long ones leave
+# fewer rows to the upper levels (1/(B - 1) of the rows in all) and fewer launches.  The products do not depend on it: the
+# first row of a block costs none in either walk, so a level of n rows costs 3 (n - blocks) and all levels 3 (rows - 1).
+# Measured with tools/bench_pair_invert.py (profiles/r16_pair_invert.json), blocks of 4 / 8 / 16 / 32 / 64: the shortest are
+# the fastest at every size and key width measured (2^12, 2^16 and 2^20 rows).
+PAIR_INVERT_BLOCK_ROWS = 4
+# EncryptedVector.dot with signed weights inverts its rows in the form from this many rows on.  Below it the present route
+# serves (the rows out of the form, phe_hip_invert_dev, phe_hip_multiexp_dev): at 3072 bits the multi-exponentiation over pair
+# rows takes about 2.4 ms longer than the one over residues whatever the length, which the inversion wins back only from 2^16
+# rows on (profiles/r16_pair_invert.json; at 1024 and 2048 bits the form wins at every size measured, from 2^8 rows on).  -vec and a - b are not slower
+# at any size measured and take the form at every length.
+PAIR_INVERT_MIN_ROWS = 1 << 16
+
 
 class ScanPlan:
     """What Engine.scan_launch_dev launches: `levels` is a list of (task_ptr uint64 (tasks + 1), carry_idx uint32 (tasks) or
@@ -587,10 +602,13 @@ class Engine:
         limbs, bits = exps if isinstance(exps, tuple) else self._exp_limbs(exps)
         neg = np.asarray(neg, dtype=bool)
         if isinstance(c, DeviceArray) and self.pair_form() and c.cols == self.pair_form() != self.ct_limbs:
-            # rows resident in the pair form, no negative scalar (the caller checked): the multi-exponentiation reads them as they
-            # are — no conversion of every ciphertext into the form (include/phe_hip.h phe_hip_pair_multiexp_rows_dev)
+            # rows resident in the pair form: the multi-exponentiation reads them as they are — no conversion of every ciphertext
+            # into the form (include/phe_hip.h phe_hip_pair_multiexp_rows_dev); the rows of negative scalars are inverted in the
+            # form first (phe_hip_pair_invert_dev), where the backend can
             if neg.any():
-                raise ValueError("pair-form rows take non-negative scalars only")
+                if not self.has_pair_invert():
+                    raise ValueError("pair-form rows take non-negative scalars only")
+                c = self._inverted_where_pair(c, neg)
             e = DeviceArray.from_host(self.ctx, limbs)
             out = DeviceArray(self.ctx, 1, self.ct_limbs)
             self.ctx.pair_multiexp_rows_dev(c.ptr, e.ptr, limbs.shape[1], bits, out.ptr, c.rows, 1)
@@ -953,6 +971,52 @@ class Engine:
         self.ctx.pair_reduce_dev(pair.ptr, pair.rows, out.ptr)
         self.ctx.sync()
         return out
+
+    # ---- inversion on resident rows (include/phe_hip.h phe_hip_pair_invert_dev) --------------------------------------------
+    def has_pair_invert(self):
+        """True when inversion has its kernel on pair rows: the pair form is offered and the backend has the entry point"""
+        return bool(self.pair_form()) and hasattr(self.ctx, "pair_invert_dev")
+
+    def pair_dot_inverts(self, rows):
+        """True when a dot product with signed weights over `rows` pair rows inverts them in the form (PAIR_INVERT_MIN_ROWS)"""
+        return self.has_pair_invert() and rows >= PAIR_INVERT_MIN_ROWS
+
+    def pair_invert_dev(self, store, block=None):
+        """out[i] = invert(store[i], n^2) on rows in the pair form, pair rows out (phe/paillier.py:745-749 without leaving the
+        form): Montgomery's trick on blocks of `block` rows (None: PAIR_INVERT_BLOCK_ROWS).  ZeroDivisionError carries the first
+        row that is not a unit as bad_index."""
+        out = DeviceArray(self.ctx, store.rows, store.cols)
+        self.ctx.pair_invert_dev(store.ptr, out.ptr, store.rows, int(PAIR_INVERT_BLOCK_ROWS if block is None else block))
+        return out
+
+    def _inverted_where_pair(self, store, neg):
+        """_inverted_where on rows in the pair form: `store` with the rows where `neg` holds replaced by their inverses, in the
+        form.  Few negative rows (under a quarter): gathered, inverted as a batch of their own, scattered into a copy; otherwise
+        the whole vector is inverted and selected per row.  ZeroDivisionError carries the row's index in store."""
+        neg = np.asarray(neg, dtype=bool)
+        count = int(neg.sum())
+        words = store.cols
+        if count * 4 < store.rows:
+            idx = np.nonzero(neg)[0].astype(np.uint32)
+            idx_d = DeviceArray.from_host(self.ctx, idx)
+            sub = DeviceArray(self.ctx, count, words)
+            self.ctx.gather_rows_dev(store.ptr, store.rows, idx_d.ptr, sub.ptr, words, count)
+            try:
+                inv = self.pair_invert_dev(sub)
+            except ZeroDivisionError as e:
+                if getattr(e, "bad_index", None) is not None and e.bad_index < count:
+                    e.bad_index = int(idx[e.bad_index])
+                raise
+            base = store.copy()
+            self.ctx.scatter_rows_dev(inv.ptr, idx_d.ptr, base.ptr, base.rows, words, count)
+            self.ctx.sync()
+            return base
+        inv = self.pair_invert_dev(store)
+        mask = DeviceArray.from_host(self.ctx, neg.astype(np.uint8), dtype=np.uint8)
+        base = DeviceArray(self.ctx, store.rows, words)
+        self.ctx.select_rows_dev(store.ptr, inv.ptr, mask.ptr, base.ptr, words, store.rows)
+        self.ctx.sync()
+        return base
 
     # ---- grouped sums on resident rows (include/phe_hip.h phe_hip_segment_reduce_dev) ------------------------------------
     def has_segment_reduce(self):

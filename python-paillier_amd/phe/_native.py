@@ -129,6 +129,7 @@ def lib():
         L.phe_hip_chacha20_rows_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ci, ci, vp, sz, vp]
         L.phe_hip_pair_powmod_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp]
         L.phe_hip_pair_multiexp_rows_dev.argtypes = [vp, vp, vp, ci, ci, vp, sz, sz, vp]
+        L.phe_hip_pair_invert_dev.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, ctypes.POINTER(sz), vp]
         _lib = L
     return _lib
 
@@ -153,6 +154,7 @@ EXPORTED_SYMBOLS = [
     "phe_hip_values_encode_dev", "phe_hip_values_decode_dev",
     "phe_hip_fixed_base_set", "phe_hip_fixed_base_info", "phe_hip_fixed_base_clear", "phe_hip_fixed_base_rows_dev",
     "phe_hip_fixed_base_pow_dev", "phe_hip_chacha20_rows_dev", "phe_hip_segment_plan_sort_dev", "phe_hip_segment_plan_level_dev",
+    "phe_hip_pair_invert_dev",
 ]
 
 
@@ -712,6 +714,14 @@ class Context:
     def invert_dev(self, a_ptr, out_ptr, batch, stream=0):
         bad = ctypes.c_size_t(0)
         rc = lib().phe_hip_invert_dev(self._h, a_ptr, out_ptr, batch, ctypes.byref(bad), stream)
+        if rc != OK:
+            _raise(rc, bad.value)
+
+    def pair_invert_dev(self, in_ptr, out_ptr, batch, block_rows=0, stream=0):
+        """out[i] = in[i]^-1 mod n^2 on rows in the pair form (phe_hip_pair_invert_dev; block_rows 0: the library's default).
+        Complete on return; ZeroDivisionError.bad_index: the first row that is not a unit"""
+        bad = ctypes.c_size_t(0)
+        rc = lib().phe_hip_pair_invert_dev(self._h, in_ptr, out_ptr, batch, block_rows, ctypes.byref(bad), stream)
         if rc != OK:
             _raise(rc, bad.value)
 

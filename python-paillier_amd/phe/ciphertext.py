@@ -643,11 +643,16 @@ class EncryptedVector(object):
     __rmul__ = __mul__
 
     def __neg__(self):
+        eng = self._eng()
+        if self.on_device and self._pair and getattr(eng, "has_pair_invert", lambda: False)():
+            # rows in the pair form: self * -1 is invert(c) of phe/paillier.py:745-749 with no power after it, taken on the pair
+            # rows themselves (Engine.pair_invert_dev) — the negation stays in the form, and a - b with it
+            return EncryptedVector(self.public_key, eng.pair_invert_dev(self._store), self._exps.copy(), _pair=True)
         return self * -1
 
     def __sub__(self, other):
         if isinstance(other, EncryptedVector):
-            return self + (other * -1)
+            return self + (-other)
         if isinstance(other, np.ndarray) and other.dtype.kind in "fi":
             return self + (-other)                                # stays on the array path of __add__
         if isinstance(other, (list, tuple, np.ndarray)):
@@ -1005,8 +1010,10 @@ class EncryptedVector(object):
             mags = mag.tolist() if isinstance(mag, np.ndarray) else mag
             powers = {d: pow(EncodedNumber.BASE, d) for d in np.unique(delta).tolist()}
             exps = [m * powers[d] for m, d in zip(mags, delta.tolist())]
-        # rows resident in the pair form and no scalar on the negative branch: the multi-exponentiation takes them as they are
-        in_form = self.on_device and self._pair and eng.pair_form() and hasattr(eng.ctx, "pair_multiexp_rows_dev") and not np.asarray(neg).any()
+        # rows resident in the pair form: the multi-exponentiation takes them as they are — with scalars on the negative branch
+        # only where the rows are inverted in the form (Engine.pair_dot_inverts, Engine.raw_dot)
+        in_form = self.on_device and self._pair and eng.pair_form() and hasattr(eng.ctx, "pair_multiexp_rows_dev") and (
+            not np.asarray(neg).any() or getattr(eng, "pair_dot_inverts", lambda rows: False)(len(self)))
         return EncryptedNumber(pk, eng.raw_dot(self._store if in_form else self._limbs, exps, neg), target)
 
     # numpy must not try to broadcast over the rows of a vector: `W @ vec`, `w @ vec`, `vec @ w` come here
